@@ -7,10 +7,15 @@ reduce-scatter amortised over more tokens: 16 -> 32 sequences +4 % (r1_v5 logs),
 profiles/r2_flagship_microbatch.log; 64 -> 96 +1.3 % at 188 GB, profiles/r2_flagship_microbatch_64_96_128.log).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gpt2-fsdp|gpt2-ddp|resnet50-ddp]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Times exactly K optimizer steps bracketed by barrier + device synchronize, takes the MAX over ranks,
 and prints ONE JSON line on rank 0 whose ``value`` is the whole-job throughput.
+A plain run does only that: set up, warm up, time the K steps, print the line.  ``--dump-outputs DIR`` also
+writes what the last timed step computed (``DIR/<name>.npy``, float32).  ``--full`` adds the measurements that
+take runs of their own: the ResNet-50 DDP ``secondary`` of the gpt2-fsdp workload and, at world > 1, the
+communication-overlap probe.
 Metric/config follow BASELINE.json ("tokens/sec GPT-2-1.3B FSDP ... at 1/2/4/8 MI355X"; ResNet-50 DDP
 samples/sec via --workload resnet50-ddp).  BASELINE.md publishes no reference number -> vs_baseline null.
 """
@@ -51,15 +56,21 @@ def parse():
     ap.add_argument("--resnet-graph", type=int, default=0,
                     help="resnet50-ddp (and the ResNet secondary): capture the whole DDP step in a HIP graph "
                          "(fwd, bwd, clip, fused AdamW; at N > 1 the bucket all-reduces too)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the ResNet-50 DDP 'secondary' of "
+                         "gpt2-fsdp (--secondary) and, at world > 1, the communication-overlap probe (--overlap-probe)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, "
+                         "rank 0): its loss and a fixed seeded sample of the parameters the optimizer stepped")
     ap.add_argument("--secondary", type=int, default=1,
-                    help="gpt2-fsdp: also measure BASELINE.json's ResNet-50 DDP metric at the same world size "
-                         "(JSON 'secondary')")
+                    help="with --full, gpt2-fsdp: also measure BASELINE.json's ResNet-50 DDP metric at the same world "
+                         "size (JSON 'secondary')")
     ap.add_argument("--secondary-micro-batch", type=int, default=None,
                     help="images per GPU of the secondary ResNet measurement (default 256)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: plumbing rehearsal of any workload on gloo (tiny --model / --micro-batch)")
     ap.add_argument("--overlap-probe", type=int, default=1,
-                    help="world > 1: after timing, measure exposed vs communication-only time (untimed)")
+                    help="with --full, world > 1: after timing, measure exposed vs communication-only time (untimed)")
     ap.add_argument("--rehearse-world", type=int, default=0,
                     help="REHEARSAL, never a headline: run this rank's step as rank --rehearse-rank of a world of "
                          "this size on ONE GPU over torch's 'fake' process group (collectives complete without "
@@ -143,9 +154,11 @@ def main():
     else:
         result = bench_resnet(args, comm, dev, world, rank)
     result["topology"] = topology(comm, dev)
-    if args.secondary and args.workload == "gpt2-fsdp":
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank)
+    if args.full and args.secondary and args.workload == "gpt2-fsdp":
         # BASELINE.json names TWO headline metrics (GPT-2-1.3B FSDP tokens/s and ResNet-50 DDP samples/s, both
-        # "at 1/2/4/8"): every run also measures the second one at the SAME world size, so each point of the
+        # "at 1/2/4/8"): a --full run also measures the second one at the SAME world size, so each point of the
         # driver's scaling curve records both.  Outside the primary's timed region; its setup and first step
         # are guarded phases (bench_resnet guarded=True): a failure on any rank skips it on every rank together
         # and the primary line is still printed.
@@ -328,7 +341,7 @@ def timed_loop(step_fn, args, comm, dev):
                        "comm_bytes_per_step": int(nbytes / args.steps)}
     if dev.type == "cuda":
         timed_loop.comm["peak_mem_gb"] = round(torch.cuda.max_memory_allocated(dev) / 1e9, 2)
-    if comm.world_size > 1 and dev.type == "cuda" and args.overlap_probe:
+    if comm.world_size > 1 and dev.type == "cuda" and args.full and args.overlap_probe:
         # diagnostics only, after the measurement: a failure here must not cost the run its JSON line
         try:
             timed_loop.comm.update(overlap_probe(step_fn, comm, dev, float(t.item()) * 1000 / args.steps))
@@ -401,6 +414,49 @@ def overlap_probe(step_fn, comm, dev, step_ms):
 def comm_fields(world):
     """Traffic of the engines per timed step, for the JSON line (zero collectives at world 1)."""
     return dict(n_ranks=world, **getattr(timed_loop, "comm", {}))
+
+
+_OUTPUTS: dict = {}
+DUMP_PARAM_SAMPLE = 1 << 22   # parameter elements kept by --dump-outputs (16 MB as float32)
+
+
+def keep_outputs(loss, params):
+    """What the timed path handed its caller in the last timed step (``--dump-outputs``): the loss tensor it
+    returned and the parameters its optimizer step wrote.  References only; nothing is copied or synchronised."""
+    _OUTPUTS.update(loss=loss, params=list(params))
+
+
+def sample_flat(tensors, k=DUMP_PARAM_SAMPLE, seed=20240607):
+    """float32 host copy of the concatenation of ``tensors`` (flattened in order) when it has at most ``k``
+    elements, else of ``k`` of its elements at sorted positions drawn once from a generator with a fixed seed:
+    the same positions in every run of the same configuration."""
+    import torch
+    sizes = [t.numel() for t in tensors]
+    total = sum(sizes)
+    if total <= k:
+        return torch.cat([t.detach().reshape(-1).float().cpu() for t in tensors])
+    g = torch.Generator()
+    g.manual_seed(seed)
+    idx = torch.randint(0, total, (k,), generator=g).sort().values
+    bounds = torch.searchsorted(idx, torch.tensor([0] + sizes).cumsum(0)).tolist()
+    out, off = [], 0
+    for t, n, lo, hi in zip(tensors, sizes, bounds[:-1], bounds[1:]):
+        if hi > lo:
+            out.append(t.detach().reshape(-1)[(idx[lo:hi] - off).to(t.device)].float().cpu())
+        off += n
+    return torch.cat(out)
+
+
+def dump_outputs(path, rank):
+    """``--dump-outputs DIR``: rank 0 writes ``DIR/loss.npy`` (the last timed step's loss, shape (1,)) and
+    ``DIR/params_sample.npy`` (``sample_flat`` of the parameters after that step; at world > 1 rank 0's shards)."""
+    import numpy as np
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), _OUTPUTS["loss"].detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "params_sample.npy"), sample_flat(_OUTPUTS["params"]).numpy())
+    log(f"[bench] outputs of the last timed step written to {path}")
 
 
 def bench_gpt2(args, comm, dev, world, rank):
@@ -518,6 +574,7 @@ def bench_gpt2(args, comm, dev, world, rank):
         torch.cuda.synchronize(dev)
         size_checkpointing()
     dt = timed_loop(step, args, comm, dev)
+    keep_outputs(state["loss"], params)
     tokens = world * mb * S * args.steps
     tps = tokens / dt
     log(f"[bench] {name} params={nparams/1e9:.3f}B loss={float(state['loss'].item()):.4f} "
@@ -592,6 +649,7 @@ def bench_resnet(args, comm, dev, world, rank, guarded=False):
     graph = bool(args.resnet_graph) and not cpu and (world == 1 or comm.backend == "nccl")
     opt = FusedAdamW(params, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=1e-4, capturable=graph)
     crit = torch.nn.CrossEntropyLoss()
+    state = {"loss": None}
 
     def step():
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=not cpu and autocast):
@@ -600,6 +658,7 @@ def bench_resnet(args, comm, dev, world, rank, guarded=False):
         _, coef, _ = clip_grad_norm_(params, args.grad_clip, comm=comm, sharded=False, apply=False)
         opt.step(grad_scale=coef)
         opt.zero_grad(set_to_none=not graph)
+        state["loss"] = loss
 
     if guarded:
         try:
@@ -635,8 +694,10 @@ def bench_resnet(args, comm, dev, world, rank, guarded=False):
         graphed = GraphedStep(body, x, y, warmup=2)
 
         def step():                                   # noqa: F811 - the graphed replacement
-            graphed(x, y)
+            state["loss"] = graphed(x, y)
     dt = timed_loop(step, args, comm, dev)
+    if not guarded:
+        keep_outputs(state["loss"], params)
     sps = world * mb * args.steps / dt
     name = "ResNet-18 DDP CPU/gloo" if cpu else "ResNet-50 DDP"
     return {"metric": f"samples/sec {name} (whole node)", "value": round(sps, 2), "unit": "samples/s",
@@ -675,11 +736,14 @@ def bench_swinir(args, comm, dev, world, rank):
     data = [(torch.rand(mb, 3, 128, 128, device=dev, generator=g), torch.rand(mb, 3, 256, 256, device=dev, generator=g))
             for _ in range(accum)]
 
+    state = {"loss": None}
+
     def step():
         for x, y in data:
             loss = tr.loss(tr.model(x), y)
             tr.backward(loss)
             tr.step()
+        state["loss"] = loss
 
     graph = bool(args.graph) and args.precision == "bf16" and (world == 1 or comm.backend == "nccl")
     if graph:
@@ -687,6 +751,7 @@ def bench_swinir(args, comm, dev, world, rank):
         eager_step = step
         step = tr.graph(eager_step)                    # noqa: F811
     dt = timed_loop(step, args, comm, dev)
+    keep_outputs(state["loss"], model.parameters())
     sps = world * mb * accum * args.steps / dt
     par = "dp{}+oss+sddp".format(world) if world > 1 else "dp1"
     return {"metric": "samples/sec SwinIR-S x2 Stoke (whole node)", "value": round(sps, 2),

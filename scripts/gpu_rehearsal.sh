@@ -23,7 +23,7 @@ run() {  # name, timeout, cmd...
 }
 for W in $WORLDS; do
   PDT_BENCH_BACKEND=gloo PDT_XGMI=1 run rehearsal_gpt2_fsdp_w$W 300 \
-    python bench.py --gpus $W --micro-batch 2 --steps 3 --warmup 1 --secondary-micro-batch 8 || exit $?
+    python bench.py --gpus $W --micro-batch 2 --steps 3 --warmup 1 --secondary-micro-batch 8 --full || exit $?
   PDT_BENCH_BACKEND=gloo PDT_XGMI=1 run rehearsal_swinir_stoke_w$W 300 \
     python bench.py --gpus $W --workload swinir-stoke --micro-batch 4 --steps 3 --warmup 1 || exit $?
 done

@@ -36,7 +36,7 @@ def test_bench_world2_reports_topology_and_secondary_headline():
     back from the process group and every rank's device in 'topology'."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--device", "cpu", "--workload", "gpt2-fsdp",
                         "--model", "gpt2-tiny", "--micro-batch", "2", "--seq", "64", "--steps", "2", "--warmup", "1",
-                        "--secondary-micro-batch", "2"], cwd=ROOT, env=_env(), capture_output=True, text=True,
+                        "--secondary-micro-batch", "2", "--full"], cwd=ROOT, env=_env(), capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -61,7 +61,7 @@ def test_bench_under_torchrun_driver_command():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
                         "--device", "cpu", "--workload", "gpt2-fsdp", "--model", "gpt2-tiny", "--micro-batch", "2",
-                        "--seq", "64", "--steps", "2", "--warmup", "1", "--secondary-micro-batch", "2"],
+                        "--seq", "64", "--steps", "2", "--warmup", "1", "--secondary-micro-batch", "2", "--full"],
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -69,6 +69,57 @@ def test_bench_under_torchrun_driver_command():
     res = json.loads(lines[0])
     assert res["n_ranks"] == 2 and res["topology"]["c10d_world"] == 2 and res["steps"] == 2
     assert res["secondary"]["config"]["parallelism"] == "dp2"
+
+
+def _plain_run(out_dir):
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--device", "cpu", "--workload", "gpt2-fsdp",
+                        "--model", "gpt2-tiny", "--micro-batch", "2", "--seq", "64", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", out_dir], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0]), r.stderr
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run times --steps steps and nothing else (no 'secondary': that is behind --full), reports
+    ms_per_step, and --dump-outputs writes the last timed step's loss and parameter sample as float32 .npy
+    files that a second run with the same arguments reproduces exactly."""
+    import numpy as np
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    res, err = _plain_run(a)
+    assert "secondary" not in res and "secondary_error" not in res
+    assert err.count("warmup step 0 done") == 1      # one measurement ran, not two
+    assert res["steps"] == 3 and res["warmup"] == 1
+    assert res["ms_per_step"] > 0 and res["unit"] == "tokens/s" and res["higher_is_better"] is True
+    assert abs(res["value"] - 2 * 64 / (res["ms_per_step"] / 1000)) <= 1e-3 * res["value"]
+    _plain_run(b)
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b)) == ["loss.npy", "params_sample.npy"]
+    total = 0
+    for name in os.listdir(a):
+        x, y = np.load(os.path.join(a, name)), np.load(os.path.join(b, name))
+        assert x.dtype == np.float32 and x.size > 0 and np.isfinite(x).all()
+        assert np.array_equal(x, y), name
+        total += x.nbytes
+    assert total <= 64 * 1024 * 1024
+    loss = float(np.load(os.path.join(a, "loss.npy"))[0])
+    assert 0.0 < loss < 20.0
+
+
+def test_bench_param_sample_is_fixed_and_bounded():
+    """The parameter sample of --dump-outputs: everything when it fits, else the same k positions every time."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ts = [torch.arange(0, 7, dtype=torch.float64), torch.arange(7, 30).reshape(23, 1).bfloat16(), torch.arange(30, 41)]
+    whole = bench.sample_flat(ts, k=41)
+    assert whole.dtype == torch.float32 and whole.tolist() == list(range(41))
+    s1, s2 = bench.sample_flat(ts, k=16), bench.sample_flat(ts, k=16)
+    assert s1.numel() == 16 and torch.equal(s1, s2)
+    assert s1.tolist() == sorted(s1.tolist()) and set(s1.tolist()) <= set(range(41))
+    assert bench.DUMP_PARAM_SAMPLE * 4 <= 64 * 1024 * 1024
 
 
 def test_bench_refuses_mismatched_world_size():
@@ -84,7 +135,7 @@ def test_bench_secondary_failure_on_one_rank_keeps_primary_line():
     still prints the primary GPT-2 line (with the reason in 'secondary_error')."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--device", "cpu", "--workload", "gpt2-fsdp",
                         "--model", "gpt2-tiny", "--micro-batch", "2", "--seq", "64", "--steps", "1", "--warmup", "1",
-                        "--secondary-micro-batch", "2"], cwd=ROOT, env=_env(PDT_BENCH_SECONDARY_FAIL_RANK="1"),
+                        "--secondary-micro-batch", "2", "--full"], cwd=ROOT, env=_env(PDT_BENCH_SECONDARY_FAIL_RANK="1"),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
