@@ -677,16 +677,23 @@ __global__ __launch_bounds__(WA_NT, 2) void win_attn_bwd_mfma(
     // relative-position-bias gradient of this workgroup's windows: the 4 waves' tiles summed in LDS
     __syncthreads();
     float* red = reinterpret_cast<float*>(BB + 64 * BP);    // [64][64] over the wave tiles
-    for (int e = threadIdx.x; e < 64 * 64; e += WA_NT) red[e] = 0.f;
-    __syncthreads();
+    // wave 0 stores, waves 1..3 add in turn: a fixed order (every wave owns each of the 64 x 64 elements once), so the
+    // gradient is bitwise reproducible -- float atomics would sum in arrival order
+#pragma unroll 1
+    for (int w = 0; w < WA_NT / 64; ++w) {
+      if (wv == w) {
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
+        for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
+          for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          atomicAdd(red + (32 * qt + l32) * 64 + 32 * kt + acc_row(r, hh), dsacc[qt][kt][r]);
-    __syncthreads();
+            for (int r = 0; r < 16; ++r) {
+              float* e = red + (32 * qt + l32) * 64 + 32 * kt + acc_row(r, hh);
+              *e = w == 0 ? dsacc[qt][kt][r] : *e + dsacc[qt][kt][r];
+            }
+      }
+      __syncthreads();
+    }
     float* dst = dbias_part + ((int64_t)pb * H + h) * N * N;
     for (int e = threadIdx.x; e < N * N; e += WA_NT) dst[e] = red[(e / N) * 64 + e % N];
   }
@@ -1050,16 +1057,23 @@ __global__ __launch_bounds__(WA_NT, 2) void win_attn_bwd_f32(
   if (PASS == 1) {
     __syncthreads();
     float* red = BB + 64 * BPF;          // [64][64] over the (now idle) wave tiles
-    for (int e = threadIdx.x; e < 64 * 64; e += WA_NT) red[e] = 0.f;
-    __syncthreads();
+    // wave 0 stores, waves 1..3 add in turn: a fixed order (every wave owns each of the 64 x 64 elements once), so the
+    // gradient is bitwise reproducible -- float atomics would sum in arrival order
+#pragma unroll 1
+    for (int w = 0; w < WA_NT / 64; ++w) {
+      if (wv == w) {
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
+        for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
+          for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          atomicAdd(red + (32 * qt + l32) * 64 + 32 * kt + acc_row(r, hh), dsacc[qt][kt][r]);
-    __syncthreads();
+            for (int r = 0; r < 16; ++r) {
+              float* e = red + (32 * qt + l32) * 64 + 32 * kt + acc_row(r, hh);
+              *e = w == 0 ? dsacc[qt][kt][r] : *e + dsacc[qt][kt][r];
+            }
+      }
+      __syncthreads();
+    }
     float* dst = dbias_part + ((int64_t)pb * H + h) * N * N;
     for (int e = threadIdx.x; e < N * N; e += WA_NT) dst[e] = red[(e / N) * 64 + e % N];
   }

@@ -98,7 +98,11 @@ class PerceptualLoss(nn.Module):
 def _l1(a, b):
     if a.is_cuda:
         from ..ops.l1 import l1_loss
-        b = b.to(a.dtype) if b.dtype != a.dtype else b
+        if b.dtype != a.dtype:
+            # F.l1_loss's type promotion: the difference is taken in the WIDER dtype (a bf16 output against an fp32
+            # target: rounding the target to bf16 first would lose every difference below the output's spacing)
+            dt = torch.promote_types(a.dtype, b.dtype)
+            a, b = a.to(dt), b.to(dt)
         if b.stride() != a.stride():
             cl = a.dim() == 4 and a.is_contiguous(memory_format=torch.channels_last)
             b = b.contiguous(memory_format=torch.channels_last) if cl else b.contiguous()

@@ -25,7 +25,8 @@ import torch.nn.functional as F
 
 from ..ops.activations import bias_gelu
 from ..ops.conv import Conv2d3x3, pixel_shuffle_affine
-from ..ops.linear import Linear, linear, linear_from_head_major, linear_head_major, linear_residual
+from ..ops.linear import (Linear, _has_hooks, from_head_major_ok, linear, linear_from_head_major, linear_head_major,
+                          linear_residual)
 from ..ops.swin_mlp import fused_mlp, fused_mlp_ok
 from ..ops.norms import LayerNorm, add_layer_norm_from_windows, layer_norm_to_windows, window_norm_ok
 from ..ops.window_attention import (fused_window_ok, head_major_ok, window_attention, window_attention_table,
@@ -103,8 +104,10 @@ class WindowAttention(nn.Module):
             qkv = linear_head_major(self.qkv, x, N, C // h) if hm else self.qkv(x)
             # bf16: the attention writes its output head-major and the projection reads it so (and its backward
             # hands dO back head-major) -- ops.linear.linear_from_head_major
-            o_hm = HEAD_MAJOR_PROJ and hm and Bw * N >= 16384 and (
-                torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype) == torch.bfloat16
+            # -- asked of the projection first (hooks, fp8, dtypes, the narrow GEMM's shapes): an output it could
+            # not read head-major is written token-major
+            o_hm = HEAD_MAJOR_PROJ and hm and from_head_major_ok(
+                self.proj, Bw * N, torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype)
             if REL_TABLE_KERNELS:
                 # the table gather and its gradient scatter fused into two small kernels (ops.window_attention)
                 out = window_attention_table(qkv, self.relative_position_bias_table, self.relative_position_index,
@@ -144,8 +147,9 @@ class Mlp(nn.Module):
             # residual added in fc2's GEMM store
             h = linear(x, self.fc1.weight)
             a = bias_gelu(h, self.fc1.bias, approximate="none")
+            # (hooks on fc2 see the module's usual call, as on the head-major paths)
             if MLP_RESIDUAL_GEMM and residual is not None and residual.dtype == a.dtype == self.fc2.weight.dtype \
-                    and not torch.is_autocast_enabled("cuda"):
+                    and not torch.is_autocast_enabled("cuda") and not _has_hooks(self.fc2):
                 return linear_residual(a, self.fc2.weight, self.fc2.bias, residual)
             y = self.fc2(a)
         else:

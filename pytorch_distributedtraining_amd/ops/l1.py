@@ -33,7 +33,11 @@ class _L1Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, go):
         (g,) = ctx.saved_tensors
-        return g.mul_(go.to(g.dtype)), None       # g is this Function's own buffer, used once
+        # out of place: the saved buffer survives a second backward of a retained graph.  One pass -- the upstream
+        # scale stays fp32 (a dimensioned fp32 operand makes fp32 the compute type), the product is rounded once
+        da = torch.empty_like(g)
+        torch.mul(g, go.detach().to(torch.float32).expand_as(g), out=da)
+        return da, None
 
 
 def l1_loss(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -724,26 +724,61 @@ def linear_head_major(module: "Linear", x: torch.Tensor, n_tok: int, head_dim: i
     return module(x)
 
 
+def from_head_major_ok(module: "Linear", rows: int, dtype: torch.dtype) -> bool:
+    """Whether ``linear_from_head_major(module, x)`` reads a head-major x ([rows, in_features] of ``dtype``, a fresh
+    contiguous buffer) on the narrow GEMM: no hooks, no fp8 region, bf16 operands (parameters as autocast casts them)
+    and a shape the kernel takes.  The producer (models.swinir.WindowAttention) asks this BEFORE it lets the window
+    attention write head-major, so the attention never writes a layout the projection has to undo."""
+    if _has_hooks(module) or fp8_enabled() or dtype != torch.bfloat16:
+        return False
+    w, b = module.weight, module.bias
+    if not torch.is_autocast_enabled("cuda") and (w.dtype != dtype or (b is not None and b.dtype != dtype)):
+        return False
+    if not (w.is_cuda and w.dim() == 2 and w.is_contiguous() and (b is None or b.is_contiguous())
+            and rows >= 16384 and _lib.available()):
+        return False
+    return bool(_lib.require().pdt_narrow_gemm_ok(rows, w.shape[1], w.shape[0]))
+
+
+class _TokenMajorFn(torch.autograd.Function):
+    """Token-major copy of a head-major tensor whose backward hands the gradient back head-major AND tagged -- the
+    producer (ops.window_attention, which wrote its output head-major) tells dO's layout by the tag alone; a plain
+    differentiable permute would return a head-major buffer it reads as token-major."""
+
+    @staticmethod
+    def forward(ctx, x, n_tok, d):
+        ctx.hm = (n_tok, d)
+        return _as_output(_token_major(x.reshape(-1, x.shape[-1]), n_tok, d).contiguous(), x.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        n_tok, d = ctx.hm
+        M, C = g.numel() // g.shape[-1], g.shape[-1]
+        dx = g.reshape(M // n_tok, n_tok, C // d, d).permute(0, 2, 1, 3).contiguous().view(g.shape)
+        dx._pdt_head_major = ctx.hm
+        return dx, None, None
+
+
 def linear_from_head_major(module: "Linear", x: torch.Tensor) -> torch.Tensor:
     """``module(x)`` for x tagged ``_pdt_head_major = (n_tok, d)`` (ops.window_attention's output written head-major):
     the narrow GEMM reads the head-major buffer directly, and its backward writes the data gradient head-major for
-    the attention's backward.  Untagged x: ``module(x)``; a tagged x the narrow path cannot take is put back
-    token-major first."""
+    the attention's backward.  Untagged x: ``module(x)``.  A tagged x the narrow path cannot take (``from_head_major_ok``
+    fails -- a producer that asked first never gets here) is put back token-major first, its gradient returned
+    head-major and tagged (``_TokenMajorFn``)."""
     hm = getattr(x, "_pdt_head_major", None)
     if hm is None:
         return module(x)
     n_tok, d = hm
-    if _has_hooks(module):     # hooks see the module's usual call on a token-major input
-        return module(_token_major(x.reshape(-1, x.shape[-1]), n_tok, d).view(x.shape))
-    w, b = module.weight, module.bias
-    if torch.is_autocast_enabled("cuda"):
-        w, b = w.to(x.dtype), (None if b is None else b.to(x.dtype))
     x2 = x.reshape(-1, x.shape[-1])
-    if (x.dtype == torch.bfloat16 and w.dtype == x.dtype and (b is None or b.dtype == x.dtype) and not fp8_enabled()
-            and x2.is_contiguous() and narrow_ok(x2, w, b)):
-        with torch.autocast("cuda", enabled=False):
-            return _LinearFn.apply(x, w, b, None, hm)
-    return module(_token_major(x2, n_tok, d).view(x.shape))
+    if from_head_major_ok(module, x2.shape[0], x.dtype):
+        w, b = module.weight, module.bias
+        if torch.is_autocast_enabled("cuda"):
+            w, b = w.to(x.dtype), (None if b is None else b.to(x.dtype))
+        if x2.is_contiguous() and narrow_ok(x2, w, b):
+            with torch.autocast("cuda", enabled=False):
+                return _LinearFn.apply(x, w, b, None, hm)
+    # hooks / fp8 / off the narrow kernel: the module's usual call on a token-major input
+    return module(_TokenMajorFn.apply(x, n_tok, d))
 
 
 class Linear(nn.Linear):
