@@ -263,7 +263,9 @@ __global__ __launch_bounds__(NT) void fp8_quant_kernel(const T* __restrict__ x, 
       uint64_t packed = 0;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        amax = fmaxf(amax, fabsf(v[k]));
+        // canonicalised: a signalling NaN fed straight into the v_max3_f32 hipcc makes of this chain comes back
+        // as a quiet NaN, which the next max drops together with the running amax (see fp8.hip amax_abs)
+        amax = fmaxf(amax, __builtin_canonicalizef(fabsf(v[k])));
         const __hip_fp8_storage_t b = __hip_cvt_float_to_fp8(v[k] * sc, __HIP_SATFINITE, __HIP_E4M3);
         packed |= (uint64_t)b << (8 * k);
       }
@@ -271,7 +273,7 @@ __global__ __launch_bounds__(NT) void fp8_quant_kernel(const T* __restrict__ x, 
     } else {
       for (int64_t j = i; j < n; ++j) {
         const float v = to_f<T>(x[j]);
-        amax = fmaxf(amax, fabsf(v));
+        amax = fmaxf(amax, __builtin_canonicalizef(fabsf(v)));
         q[j] = __hip_cvt_float_to_fp8(v * sc, __HIP_SATFINITE, __HIP_E4M3);
       }
     }

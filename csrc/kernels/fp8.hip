@@ -11,6 +11,11 @@
 //    a module's tensor slots in ONE launch: push the last iteration's amax into the history, clear it,
 //    scale = fmax / max(history) / 2^margin, scale_inv = 1 / scale.  Keeps the whole recipe on the device
 //    (no host sync per layer).
+//
+// Non-finite contract of every cast here and of pdt_fp8_quant (the torch path of ops/fp8.py matches it): a finite
+// x * scale saturates at +-fmax, a NaN or +-inf x * scale reaches the conversion unclamped (NaN of either sign ->
+// 0xff in e4m3fn / 0xfe in e5m2, +-inf -> 0x7f / 0xff in e4m3fn, which has no inf, and 0x7c / 0xfc in e5m2), and the
+// amax ignores NaN inputs while +-inf counts.
 #include "common.h"
 #include "reduce.h"
 
@@ -34,6 +39,11 @@ __device__ __forceinline__ float gelu_tanh_grad(float u) {
   const float s = sig2z(u);
   return s + 2.f * u * s * (1.f - s) * 0.7978845608028654f * (1.f + 3.f * 0.044715f * u * u);
 }
+
+// |v| as an amax operand.  Canonicalised explicitly: hipcc folds fmaxf chains over freshly loaded values into bare
+// v_max3_f32, which turns a signalling NaN operand into a quiet NaN result, and the next max then drops that NaN
+// together with the running amax (every value seen before the NaN was lost).  A quiet NaN is simply skipped.
+__device__ __forceinline__ float amax_abs(float v) { return __builtin_canonicalizef(fabsf(v)); }
 
 template <int FMT>
 __device__ __forceinline__ uint8_t to_fp8(float v) {
@@ -113,7 +123,7 @@ __global__ __launch_bounds__(256) void fp8_cast_transpose_kernel(const T* __rest
       uint32_t lo = 0, hi = 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        amax = fmaxf(amax, fmaxf(fabsf(v[k]), fabsf(v[k + 4])));
+        amax = fmaxf(amax, fmaxf(amax_abs(v[k]), amax_abs(v[k + 4])));
         lo |= (uint32_t)to_fp8<FMT>(v[k] * sc) << (8 * k);
         hi |= (uint32_t)to_fp8<FMT>(v[k + 4] * sc) << (8 * k);
       }
@@ -223,7 +233,7 @@ __global__ __launch_bounds__(256) void fp8_ct128_kernel(const T* __restrict__ x,
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float e = v[4 * j + k];
-          amax = fmaxf(amax, fabsf(e));
+          amax = fmaxf(amax, amax_abs(e));
           w[j] |= (uint32_t)to_fp8<FMT>(e * sc) << (8 * k);
         }
       }

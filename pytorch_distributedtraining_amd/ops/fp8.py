@@ -10,14 +10,33 @@ from . import _lib
 E4M3_MAX = 448.0
 
 
+_NAN_CODE = {torch.float8_e4m3fn: 0xFF, torch.float8_e5m2: 0xFE}   # what gfx950's conversion returns for any NaN
+
+
+def _sat_cast(p: torch.Tensor, fmax: float, dt: torch.dtype) -> torch.Tensor:
+    """fp32 ``p`` -> fp8 as the kernels do it: finite values saturate at +-fmax, NaN and +-inf skip the clamp
+    (+-inf -> 0x7f / 0xff in e4m3fn, which has no inf, 0x7c / 0xfc in e5m2; NaN of either sign -> _NAN_CODE)."""
+    q = torch.where(torch.isfinite(p), p.clamp(-fmax, fmax), p).to(dt)
+    q.view(torch.uint8).masked_fill_(torch.isnan(p), _NAN_CODE[dt])
+    return q
+
+
+def _amax_skip_nan(xf: torch.Tensor) -> torch.Tensor:
+    """max |x| over the non-NaN elements (the kernels' fmaxf drops NaN; +-inf counts), shape [1]."""
+    a = xf.abs()
+    return torch.where(torch.isnan(a), torch.zeros_like(a), a).amax().reshape(1)
+
+
 def quantize_fp8(x: torch.Tensor, scale: torch.Tensor, amax: torch.Tensor | None = None):
     """Return uint8 storage of fp8-e4m3fn(x * scale) (saturating); optionally max-accumulate |x| into
-    ``amax`` (fp32 [1], reinterpreted as uint32 bits by the kernel, so it must start >= 0)."""
+    ``amax`` (fp32 [1], reinterpreted as uint32 bits by the kernel, so it must start >= 0).
+    Non-finite contract (kernel and torch path alike): a finite x * scale saturates at +-448, a NaN or +-inf
+    x * scale is converted unclamped so it stays visible as the NaN code, and amax ignores NaN inputs."""
     x = x.contiguous()
     if not x.is_cuda:
-        q = (x.float() * scale.float()).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+        q = _sat_cast(x.float() * scale.float(), E4M3_MAX, torch.float8_e4m3fn)
         if amax is not None:
-            amax.copy_(torch.maximum(amax, x.abs().max().float().reshape(1)))
+            amax.copy_(torch.maximum(amax, _amax_skip_nan(x.float())))
         return q.view(torch.uint8)
     q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     _lib.call("pdt_fp8_quant", x.data_ptr(), q.data_ptr(), x.numel(), _lib.dtype_code(x.dtype), scale.data_ptr(),
@@ -127,7 +146,9 @@ class Fp8Meta:
         self.cur[s0:s1] = 0
         m = h.amax(dim=1)
         ok = (m > 0) & torch.isfinite(m)
-        new = torch.where(ok, fmax / torch.where(ok, m, torch.ones_like(m)) * mul, self.scale[s0:s1])
+        # tensor / tensor: ``float / tensor`` is reciprocal-then-multiply in torch, one ulp off the kernel's division
+        new = torch.where(ok, torch.full_like(m, fmax) / torch.where(ok, m, torch.ones_like(m)) * mul,
+                          self.scale[s0:s1])
         self.scale[s0:s1] = new
         self.scale_inv[s0:s1] = 1.0 / new
 
@@ -154,7 +175,9 @@ def _ct_ok(x: torch.Tensor) -> bool:
 
 def cast_transpose(x: torch.Tensor, meta: Fp8Meta, slot: int, fmt: int, want_q: bool = True, want_t: bool = True):
     """fp8(x * scale[slot]) as [R, C] and / or its transpose [C, R]; max-accumulates |x| into meta.cur[slot].
-    Returns (q or None, qt or None) as torch fp8 tensors."""
+    Returns (q or None, qt or None) as torch fp8 tensors.
+    Non-finite contract (kernels and torch path alike): a finite x * scale saturates at +-fmax, a NaN or +-inf
+    x * scale is converted unclamped (NaN code in e4m3fn, inf / NaN codes in e5m2), and the amax ignores NaN."""
     R, C = x.shape
     dt = _FMT_DTYPE[fmt]
     if _ct_ok(x):
@@ -166,11 +189,10 @@ def cast_transpose(x: torch.Tensor, meta: Fp8Meta, slot: int, fmt: int, want_q: 
         return q, qt
     # reference path (CPU tests, shapes the tile kernel does not take)
     xf = x.float()
-    meta.cur[slot:slot + 1].copy_(torch.maximum(meta.cur[slot:slot + 1], xf.abs().amax().reshape(1)))
+    meta.cur[slot:slot + 1].copy_(torch.maximum(meta.cur[slot:slot + 1], _amax_skip_nan(xf)))
     if not (want_q or want_t):
         return None, None
-    fmax = _FMT_MAX[fmt]
-    q = (xf * meta.scale[slot]).clamp(-fmax, fmax).to(dt)
+    q = _sat_cast(xf * meta.scale[slot], _FMT_MAX[fmt], dt)
     return (q if want_q else None), (q.t().contiguous() if want_t else None)
 
 
