@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void window_perm_kernel(const T* __restrict__ 
 }  // namespace
 
 // reverse = 0: windows = partition(roll(x, -shift)); reverse = 1: x = roll(reverse(windows), +shift) (+ res).
-// C % 4 == 0, H % ws == 0, W % ws == 0, 0 <= shift < ws.
+// C % 4 == 0, H % ws == 0, W % ws == 0, 0 <= shift < ws.  dtype: kF32 / kBF16.
 namespace {
 template <typename T>
 int window_perm_launch(const void* src, const void* res, void* dst, int64_t rows, int C, int H, int W, int ws,
@@ -233,12 +233,10 @@ int window_perm_launch(const void* src, const void* res, void* dst, int64_t rows
 }
 }  // namespace
 PDT_API int pdt_window_perm(const void* src, const void* res, void* dst, int64_t rows, int C, int H, int W, int ws,
-                            int shift, int reverse, hipStream_t st) {
-  return window_perm_launch<bf16_t>(src, res, dst, rows, C, H, W, ws, shift, reverse, st);
-}
-PDT_API int pdt_window_perm_f32(const void* src, const void* res, void* dst, int64_t rows, int C, int H, int W, int ws,
-                                int shift, int reverse, hipStream_t st) {
-  return window_perm_launch<float>(src, res, dst, rows, C, H, W, ws, shift, reverse, st);
+                            int shift, int reverse, int dt, hipStream_t st) {
+  if (dt == kBF16) return window_perm_launch<bf16_t>(src, res, dst, rows, C, H, W, ws, shift, reverse, st);
+  if (dt == kF32) return window_perm_launch<float>(src, res, dst, rows, C, H, W, ws, shift, reverse, st);
+  return (int)hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -702,7 +702,7 @@ __global__ __launch_bounds__(WA_NT, 2) void win_attn_bwd_mfma(
 size_t fwd_mfma_lds() { return (size_t)2 * (64 * BP + 4 * FWD_WAVE); }
 size_t bwd_mfma_lds() { return (size_t)2 * (64 * BP + 4 * BWD_WAVE); }
 bool mfma_ok(int N, int H, int d, int dt) {
-  return dt == kBF16 && d >= 2 && d <= 16 && d % 2 == 0 && N >= 1 && N <= 64 && H >= 1;
+  return (dt == kBF16 || dt == kF32) && d >= 2 && d <= 16 && d % 2 == 0 && N >= 1 && N <= 64 && H >= 1;
 }
 // workgroups per head: 4 waves each, ~`per_cu` workgroups per CU over all heads
 int mfma_blocks_per_head(int Bw, int H, int per_cu) {
@@ -1079,60 +1079,6 @@ __global__ __launch_bounds__(WA_NT, 2) void win_attn_bwd_f32(
   }
 }
 
-template <int D>
-int wa_f32_fwd_launch(const float* qkv, const float* bias, const float* mask, const uint8_t* labels, int nw, float* o,
-                      float* lse, int Bw, int N, int H, float scale, const WaLayout& LY, float* hm_out,
-                      hipStream_t st) {
-  const int P = mfma_blocks_per_head(Bw, H, 4);
-  const size_t lds = f32_fwd_lds<D>();
-  const bool full = N == 64;
-#define PDT_WF(M, F) \
-  win_attn_fwd_f32<D, M, F><<<P * H, WA_NT, lds, st>>>(qkv, bias, mask, labels, nw, o, lse, Bw, N, H, scale, P, LY, \
-                                                       hm_out)
-  if (labels) { if (full) PDT_WF(2, true); else PDT_WF(2, false); }
-  else if (mask) { if (full) PDT_WF(1, true); else PDT_WF(1, false); }
-  else { if (full) PDT_WF(0, true); else PDT_WF(0, false); }
-#undef PDT_WF
-  return (int)hipGetLastError();
-}
-template <int D>
-int wa_f32_bwd_launch(const float* qkv, const float* bias, const float* mask, const uint8_t* labels, int nw,
-                      const float* o, const float* dout, const float* lse, float* dqkv, float* dbias_part, int Bw,
-                      int N, int H, float scale, const WaLayout& LY, hipStream_t st) {
-  const int P = mfma_blocks_per_head(Bw, H, 2);
-  const size_t lds = f32_bwd_lds<D>();
-  static bool attr = [] {
-    bool ok = true;
-    const void* fns[12] = {
-        (const void*)win_attn_bwd_f32<D, 1, true, 1>,  (const void*)win_attn_bwd_f32<D, 1, false, 1>,
-        (const void*)win_attn_bwd_f32<D, 0, true, 1>,  (const void*)win_attn_bwd_f32<D, 0, false, 1>,
-        (const void*)win_attn_bwd_f32<D, 1, true, 2>,  (const void*)win_attn_bwd_f32<D, 1, false, 2>,
-        (const void*)win_attn_bwd_f32<D, 0, true, 2>,  (const void*)win_attn_bwd_f32<D, 0, false, 2>,
-        (const void*)win_attn_bwd_f32<D, 2, true, 1>,  (const void*)win_attn_bwd_f32<D, 2, false, 1>,
-        (const void*)win_attn_bwd_f32<D, 2, true, 2>,  (const void*)win_attn_bwd_f32<D, 2, false, 2>};
-    for (const void* f : fns)
-      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f32_bwd_lds<D>()) == hipSuccess;
-    return ok;
-  }();
-  if (!attr) return (int)hipErrorInvalidValue;
-  const bool full = N == 64;
-#define PDT_WB(M, F, PS)                                                                                         \
-  win_attn_bwd_f32<D, M, F, PS><<<P * H, WA_NT, lds, st>>>(qkv, bias, mask, labels, nw, o, dout, lse, dqkv, dbias_part, \
-                                                           Bw, N, H, scale, P, LY)
-  if (labels) {
-    if (full) { PDT_WB(2, true, 1); PDT_WB(2, true, 2); }
-    else { PDT_WB(2, false, 1); PDT_WB(2, false, 2); }
-  } else if (mask) {
-    if (full) { PDT_WB(1, true, 1); PDT_WB(1, true, 2); }
-    else { PDT_WB(1, false, 1); PDT_WB(1, false, 2); }
-  } else {
-    if (full) { PDT_WB(0, true, 1); PDT_WB(0, true, 2); }
-    else { PDT_WB(0, false, 1); PDT_WB(0, false, 2); }
-  }
-#undef PDT_WB
-  return (int)hipGetLastError();
-}
-
 }  // namespace
 
 namespace {
@@ -1225,59 +1171,64 @@ PDT_API int pdt_win_attn_mfma_ok(int N, int H, int d, int dt) { return mfma_ok(N
 // number of relative-bias-gradient partials [P, H, N, N] the backward writes
 PDT_API int pdt_win_attn_mfma_grid(int Bw, int H) { return mfma_blocks_per_head(Bw, H, 2); }
 
-#define PDT_WA_DISPATCH_D(d, CALL) \
-  switch (d) {                      \
-    case 2: CALL(2); break;         \
-    case 4: CALL(4); break;         \
-    case 6: CALL(6); break;         \
-    case 8: CALL(8); break;         \
-    case 10: CALL(10); break;       \
-    case 12: CALL(12); break;       \
-    case 14: CALL(14); break;       \
-    default: CALL(16); break;       \
-  }
-
 namespace {
-template <int D>
+// What the host side needs to know about a kernel family: element type, kernel templates, dynamic LDS bytes
+struct WaBF16 {
+  using T = bf16_t;
+  template <int D, int MK, bool FULL> static constexpr auto fwd = win_attn_fwd_mfma<D, MK, FULL>;
+  template <int D, int MK, bool FULL, int PASS> static constexpr auto bwd = win_attn_bwd_mfma<D, MK, FULL, PASS>;
+  template <int D> static size_t fwd_lds() { return fwd_mfma_lds(); }
+  template <int D> static size_t bwd_lds() { return bwd_mfma_lds(); }
+};
+struct WaF32 {
+  using T = float;
+  template <int D, int MK, bool FULL> static constexpr auto fwd = win_attn_fwd_f32<D, MK, FULL>;
+  template <int D, int MK, bool FULL, int PASS> static constexpr auto bwd = win_attn_bwd_f32<D, MK, FULL, PASS>;
+  template <int D> static size_t fwd_lds() { return f32_fwd_lds<D>(); }
+  template <int D> static size_t bwd_lds() { return f32_bwd_lds<D>(); }
+};
+
+template <typename TR, int D>
 int wa_fwd_launch(const void* qkv, const float* bias, const float* mask, const uint8_t* labels, int nw, void* o,
                   float* lse, int Bw, int N, int H, float scale, const WaLayout& LY, void* hm_out, hipStream_t st) {
+  using T = typename TR::T;
   const int P = mfma_blocks_per_head(Bw, H, 4);
-  const size_t lds = fwd_mfma_lds();
+  const size_t lds = TR::template fwd_lds<D>();
   const bool full = N == 64;
-#define PDT_WF(M, F)                                                                                          \
-  win_attn_fwd_mfma<D, M, F><<<P * H, WA_NT, lds, st>>>((const bf16_t*)qkv, bias, mask, labels, nw, (bf16_t*)o, \
-                                                        lse, Bw, N, H, scale, P, LY, (bf16_t*)hm_out)
+#define PDT_WF(M, F)                                                                                              \
+  TR::template fwd<D, M, F><<<P * H, WA_NT, lds, st>>>((const T*)qkv, bias, mask, labels, nw, (T*)o, lse, Bw, N, H, \
+                                                       scale, P, LY, (T*)hm_out)
   if (labels) { if (full) PDT_WF(2, true); else PDT_WF(2, false); }
   else if (mask) { if (full) PDT_WF(1, true); else PDT_WF(1, false); }
   else { if (full) PDT_WF(0, true); else PDT_WF(0, false); }
 #undef PDT_WF
   return (int)hipGetLastError();
 }
-template <int D>
+template <typename TR, int D>
 int wa_bwd_launch(const void* qkv, const float* bias, const float* mask, const uint8_t* labels, int nw, const void* o,
                   const void* dout, const float* lse, void* dqkv, float* dbias_part, int Bw, int N, int H, float scale,
                   const WaLayout& LY, hipStream_t st) {
+  using T = typename TR::T;
   const int P = mfma_blocks_per_head(Bw, H, 2);
-  const size_t lds = bwd_mfma_lds();
+  const size_t lds = TR::template bwd_lds<D>();
   static bool attr = [] {
     bool ok = true;
-    const void* fns[12] = {
-        (const void*)win_attn_bwd_mfma<D, 1, true, 1>,  (const void*)win_attn_bwd_mfma<D, 1, false, 1>,
-        (const void*)win_attn_bwd_mfma<D, 0, true, 1>,  (const void*)win_attn_bwd_mfma<D, 0, false, 1>,
-        (const void*)win_attn_bwd_mfma<D, 1, true, 2>,  (const void*)win_attn_bwd_mfma<D, 1, false, 2>,
-        (const void*)win_attn_bwd_mfma<D, 0, true, 2>,  (const void*)win_attn_bwd_mfma<D, 0, false, 2>,
-        (const void*)win_attn_bwd_mfma<D, 2, true, 1>,  (const void*)win_attn_bwd_mfma<D, 2, false, 1>,
-        (const void*)win_attn_bwd_mfma<D, 2, true, 2>,  (const void*)win_attn_bwd_mfma<D, 2, false, 2>};
+#define PDT_K(M, F, PS) (const void*)TR::template bwd<D, M, F, PS>
+    const void* fns[12] = {PDT_K(1, true, 1), PDT_K(1, false, 1), PDT_K(0, true, 1), PDT_K(0, false, 1),
+                           PDT_K(1, true, 2), PDT_K(1, false, 2), PDT_K(0, true, 2), PDT_K(0, false, 2),
+                           PDT_K(2, true, 1), PDT_K(2, false, 1), PDT_K(2, true, 2), PDT_K(2, false, 2)};
+#undef PDT_K
     for (const void* f : fns)
-      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_mfma_lds()) == hipSuccess;
+      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)TR::template bwd_lds<D>()) == hipSuccess;
     return ok;
   }();
   if (!attr) return (int)hipErrorInvalidValue;
   const bool full = N == 64;
-#define PDT_WB(M, F, PS)                                                                                           \
-  win_attn_bwd_mfma<D, M, F, PS><<<P * H, WA_NT, lds, st>>>((const bf16_t*)qkv, bias, mask, labels, nw,              \
-                                                            (const bf16_t*)o, (const bf16_t*)dout, lse, (bf16_t*)dqkv, \
-                                                            dbias_part, Bw, N, H, scale, P, LY)
+#define PDT_WB(M, F, PS)                                                                                       \
+  TR::template bwd<D, M, F, PS><<<P * H, WA_NT, lds, st>>>((const T*)qkv, bias, mask, labels, nw, (const T*)o, \
+                                                           (const T*)dout, lse, (T*)dqkv, dbias_part, Bw, N, H, scale, \
+                                                           P, LY)
   if (labels) {
     if (full) { PDT_WB(2, true, 1); PDT_WB(2, true, 2); }
     else { PDT_WB(2, false, 1); PDT_WB(2, false, 2); }
@@ -1291,8 +1242,22 @@ int wa_bwd_launch(const void* qkv, const float* bias, const float* mask, const u
 #undef PDT_WB
   return (int)hipGetLastError();
 }
+
+// One family's launchers by head dim: entry d / 2 - 1 (mfma_ok: d even, 2..16).  A family's forward and backward sit
+// in one object so that they are instantiated together, the bf16 family first: the order of the kernels in the code
+// object follows it.
+template <typename TR>
+struct WaLaunchers {
+  decltype(&wa_fwd_launch<TR, 2>) fwd[8];
+  decltype(&wa_bwd_launch<TR, 2>) bwd[8];
+};
+#define PDT_BY_D(F) {F<TR, 2>, F<TR, 4>, F<TR, 6>, F<TR, 8>, F<TR, 10>, F<TR, 12>, F<TR, 14>, F<TR, 16>}
+template <typename TR>
+constexpr WaLaunchers<TR> wa_launchers = {PDT_BY_D(wa_fwd_launch), PDT_BY_D(wa_bwd_launch)};
+#undef PDT_BY_D
 }  // namespace
 
+// dt: kBF16 (bf16 MFMA kernels) or kF32 (exact-f32 MFMA kernels); qkv, o, dout, dqkv and hm_out are of that type.
 // mask [nw, N, N] fp32 or null; labels [nw, N] uint8 region labels or null (takes precedence over mask:
 // mask value = -100 where the query's and key's labels differ, 0 elsewhere)
 // qkv token-major [Bw, N, 3C], or head-major [Bw, 3, H, N, d] with q_hm = 1 (the narrow GEMM's head-major output);
@@ -1300,57 +1265,25 @@ int wa_bwd_launch(const void* qkv, const float* bias, const float* mask, const u
 // (hm = 1), written from the staged slices
 PDT_API int pdt_win_attn_mfma_fwd(const void* qkv, const float* bias, const float* mask, const void* labels, int nw,
                                   void* o, float* lse, int Bw, int N, int H, int d, float scale, void* hm_out,
-                                  int q_hm, int o_hm, hipStream_t st) {
-  if (!mfma_ok(N, H, d, kBF16) || Bw <= 0 || ((mask || labels) && nw <= 0) || (q_hm && hm_out))
+                                  int q_hm, int o_hm, int dt, hipStream_t st) {
+  if (!mfma_ok(N, H, d, dt) || Bw <= 0 || ((mask || labels) && nw <= 0) || (q_hm && hm_out))
     return (int)hipErrorInvalidValue;
   const WaLayout LY = wa_layout(N, H, d, q_hm, 0, nullptr, o_hm);
-#define PDT_C(D) \
-  return wa_fwd_launch<D>(qkv, bias, mask, (const uint8_t*)labels, nw, o, lse, Bw, N, H, scale, LY, hm_out, st)
-  PDT_WA_DISPATCH_D(d, PDT_C)
-#undef PDT_C
+  const auto launch = dt == kBF16 ? wa_launchers<WaBF16>.fwd[d / 2 - 1] : wa_launchers<WaF32>.fwd[d / 2 - 1];
+  return launch(qkv, bias, mask, (const uint8_t*)labels, nw, o, lse, Bw, N, H, scale, LY, hm_out, st);
 }
 
 // dqkv [Bw, N, 3C] fully written; dbias_part [pdt_win_attn_mfma_grid(Bw, H), H, N, N] fp32 fully written
 PDT_API int pdt_win_attn_mfma_bwd(const void* qkv, const float* bias, const float* mask, const void* labels, int nw,
                                   const void* o, const void* dout, const float* lse, void* dqkv, float* dbias_part,
-                                  int Bw, int N, int H, int d, float scale, int hm, const float* delta,
+                                  int Bw, int N, int H, int d, float scale, int hm, const float* delta, int dt,
                                   hipStream_t st) {
-  if (!mfma_ok(N, H, d, kBF16) || Bw <= 0 || ((mask || labels) && nw <= 0) || (hm && !delta))
+  if (!mfma_ok(N, H, d, dt) || Bw <= 0 || ((mask || labels) && nw <= 0) || (hm && !delta))
     return (int)hipErrorInvalidValue;
   const WaLayout LY = wa_layout(N, H, d, hm, hm, delta);
-#define PDT_C(D)                                                                                                   \
-  return wa_bwd_launch<D>(qkv, bias, mask, (const uint8_t*)labels, nw, o, dout, lse, dqkv, dbias_part, Bw, N, H, \
-                          scale, LY, st)
-  PDT_WA_DISPATCH_D(d, PDT_C)
-#undef PDT_C
+  const auto launch = dt == kBF16 ? wa_launchers<WaBF16>.bwd[d / 2 - 1] : wa_launchers<WaF32>.bwd[d / 2 - 1];
+  return launch(qkv, bias, mask, (const uint8_t*)labels, nw, o, dout, lse, dqkv, dbias_part, Bw, N, H, scale, LY, st);
 }
-// fp32 MFMA path (same contract as the bf16 one; partials [pdt_win_attn_mfma_grid(Bw, H), H, N, N])
-PDT_API int pdt_win_attn_mfma32_ok(int N, int H, int d) { return mfma_ok(N, H, d, kBF16) ? 1 : 0; }
-PDT_API int pdt_win_attn_mfma32_fwd(const float* qkv, const float* bias, const float* mask, const void* labels, int nw,
-                                    float* o, float* lse, int Bw, int N, int H, int d, float scale, float* hm_out,
-                                    int q_hm, int o_hm, hipStream_t st) {
-  if (!mfma_ok(N, H, d, kBF16) || Bw <= 0 || ((mask || labels) && nw <= 0) || (q_hm && hm_out))
-    return (int)hipErrorInvalidValue;
-  const WaLayout LY = wa_layout(N, H, d, q_hm, 0, nullptr, o_hm);
-#define PDT_C(D) \
-  return wa_f32_fwd_launch<D>(qkv, bias, mask, (const uint8_t*)labels, nw, o, lse, Bw, N, H, scale, LY, hm_out, st)
-  PDT_WA_DISPATCH_D(d, PDT_C)
-#undef PDT_C
-}
-PDT_API int pdt_win_attn_mfma32_bwd(const float* qkv, const float* bias, const float* mask, const void* labels, int nw,
-                                    const float* o, const float* dout, const float* lse, float* dqkv,
-                                    float* dbias_part, int Bw, int N, int H, int d, float scale, int hm,
-                                    const float* delta, hipStream_t st) {
-  if (!mfma_ok(N, H, d, kBF16) || Bw <= 0 || ((mask || labels) && nw <= 0) || (hm && !delta))
-    return (int)hipErrorInvalidValue;
-  const WaLayout LY = wa_layout(N, H, d, hm, hm, delta);
-#define PDT_C(D)                                                                                                 \
-  return wa_f32_bwd_launch<D>(qkv, bias, mask, (const uint8_t*)labels, nw, o, dout, lse, dqkv, dbias_part, Bw, N, \
-                              H, scale, LY, st)
-  PDT_WA_DISPATCH_D(d, PDT_C)
-#undef PDT_C
-}
-#undef PDT_WA_DISPATCH_D
 
 // qkv [Bw, N, 3, H, d] (= [Bw, N, 3C]); bias_t [H, N(j), N(i)] fp32 (dense relative-position bias,
 // transposed); mask_t [nw, N(j), N(i)] fp32 or null (window bw uses mask bw % nw); o [Bw, N, C]; lse [Bw, H, N]

@@ -11,7 +11,9 @@ exists for the CPU unit tests and the gloo multi-process tests.
 from __future__ import annotations
 
 import ctypes
+import glob
 import os
+import re
 import threading
 
 import torch
@@ -28,176 +30,48 @@ c_int = ctypes.c_int
 c_int64 = ctypes.c_int64
 c_float = ctypes.c_float
 
-# name -> argtypes (restype is always c_int)
-_SIGS = {
-    "pdt_adamw_mt": [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
-                     c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pdt_step_inc": [c_void_p, c_void_p, c_void_p],
-    "pdt_lt_probe": [c_int, c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int],
-    "pdt_lt_matmul": [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                      c_void_p, c_int, c_int, c_void_p],
-    "pdt_lt_matmul_c": [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                        c_int, c_int, c_int, c_void_p],
-    "pdt_embedding_bwd": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_void_p],
-    "pdt_l2norm_mt": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
-    "pdt_clip_coef": [c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pdt_scale_mt": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
-    "pdt_cast_f32_bf16_mt": [c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "pdt_copy_mt": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "pdt_add_mt": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "pdt_norm_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                     c_int, c_float, c_int, c_int, c_int, c_void_p],
-    "pdt_norm_bwd_workspace_floats": [c_int, c_int],
-    "pdt_norm_fwd_win": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                         c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "pdt_norm_bwd_win": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                         c_void_p],
-    "pdt_norm_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                     c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "pdt_colsum_ws_floats": [c_int, c_int],
-    "pdt_bias_gelu_bwd_db": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                             c_int, c_int, c_int, c_void_p],
-    "pdt_colsum": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p],
-    "pdt_bias_gelu_fwd": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],
-    "pdt_bias_gelu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],
-    "pdt_swiglu_fwd": [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p],
-    "pdt_swiglu_bwd": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p],
-    "pdt_rope": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int,
-                 c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "pdt_fp8_quant": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
-    "pdt_fp8_dequant": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p],
-    "pdt_fp8_cast_transpose": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                               c_void_p],
-    "pdt_fp8_update_scales": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
-                              c_void_p],
-    "pdt_fp8_gelu_bwd_ws_floats": [c_int, c_int],
-    "pdt_fp8_bias_gelu_ct": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "pdt_fp8_bias_gelu_bwd_ct": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                 c_int, c_void_p, c_void_p, c_void_p],
-    "pdt_cast_f32_bf16": [c_void_p, c_void_p, c_int64, c_void_p],
-    "pdt_transpose16": [c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "pdt_ce_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_void_p],
-    "pdt_ce_fwd_grad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int,
-                        c_void_p],
-    "pdt_ce_scale": [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p],
-    "pdt_ce_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64,
-                   c_int, c_int, c_void_p],
-    "pdt_flash_attn_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                           c_int, c_int, c_float, c_int, c_void_p],
-    "pdt_flash_attn_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                           c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
-                           c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    "pdt_flash_attn_colsum_ws_floats": [c_int, c_int, c_int, c_int, c_int, c_int],
-    "pdt_flash_attn_set_dkdv": [c_int],
-    "pdt_flash_attn_set_dqp": [c_int],
-    "pdt_flash_attn_set_variant": [c_int, c_int],
-    "pdt_flash_attn_set_order": [c_int],
-    "pdt_win_attn_grid": [c_int],
-    "pdt_win_attn_mfma_ok": [c_int, c_int, c_int, c_int],
-    "pdt_win_attn_mfma_grid": [c_int, c_int],
-    "pdt_win_attn_mfma_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                              c_int, c_float, c_void_p, c_int, c_int, c_void_p],
-    "pdt_win_bwd_prep": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                         c_void_p],
-    "pdt_rel_bias_gather": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "pdt_rel_bias_scatter": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                             c_void_p],
-    "pdt_win_attn_mfma_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p],
-    "pdt_win_attn_mfma32_ok": [c_int, c_int, c_int],
-    "pdt_win_attn_mfma32_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                                c_int, c_float, c_void_p, c_int, c_int, c_void_p],
-    "pdt_win_attn_mfma32_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p],
-    "pdt_win_attn_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
-                         c_int, c_void_p],
-    "pdt_win_attn_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
-    "pdt_xgmi_alloc": [c_int64, c_int, c_void_p],
-    "pdt_xgmi_free": [c_void_p],
-    "pdt_xgmi_ipc_get": [c_void_p, c_void_p],
-    "pdt_xgmi_ipc_handle_bytes": [],
-    "pdt_xgmi_ipc_open": [c_void_p, c_void_p],
-    "pdt_xgmi_ipc_close": [c_void_p],
-    "pdt_xgmi_error": [c_void_p, c_void_p],
-    "pdt_xgmi_collective": [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p, c_int, c_int,
-                            ctypes.c_uint, c_int64, ctypes.c_uint, c_void_p, c_void_p],
-    "pdt_xgmi_host_flag_alloc": [c_void_p, c_void_p],
-    "pdt_xgmi_host_flag_free": [c_void_p],
-    "pdt_xgmi_wallclock_khz": [],
-    "pdt_bn_ws_floats": [c_int],
-    "pdt_bn_ok": [c_int],
-    "pdt_maxpool_ok": [c_int, c_int, c_int, c_int],
-    "pdt_bn_stats_finalize": [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pdt_maxpool_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                        c_void_p],
-    "pdt_maxpool_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                        c_void_p],
-    "pdt_bn_stats": [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
-    "pdt_bn_finalize": [c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                        c_void_p, c_void_p, c_void_p, c_void_p],
-    "pdt_bn_eval_coef": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pdt_bn_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p],
-    "pdt_bn_bwd_reduce": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
-                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pdt_bn_bwd_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                         c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p],
-    "pdt_conv3x3_igemm_ok": [c_int, c_int, c_int, c_int, c_int],
-    "pdt_conv3x3_igemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "pdt_conv3x3_igemm_act": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                              c_void_p],
-    "pdt_l1_partials": [c_int64],
-    "pdt_l1_fwd_grad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
-    "pdt_narrow_gemm_f32_ok": [c_int64, c_int, c_int],
-    "pdt_narrow_gemm_f32_partials": [c_int64],
-    "pdt_narrow_gemm_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
-                            c_int, c_int, c_void_p, c_void_p],
-    "pdt_narrow_wgrad_f32_ok": [c_int64, c_int, c_int],
-    "pdt_narrow_wgrad_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p],
-    "pdt_narrow_wgrad_ok": [c_int64, c_int, c_int],
-    "pdt_narrow_wgrad_ws_floats": [c_int64, c_int, c_int],
-    "pdt_narrow_wgrad": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
-    "pdt_narrow_gemm_ok": [c_int64, c_int, c_int],
-    "pdt_narrow_gemm_partials": [c_int64, c_int, c_int],
-    "pdt_narrow_gemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p,
-                        c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    "pdt_window_perm": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "pdt_window_perm_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "pdt_im2col3x3": [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                      c_int, c_void_p],
-    "pdt_pixel_shuffle_affine_fwd": [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int,
-                                     c_float, c_void_p, c_void_p, c_int, c_void_p],
-    "pdt_pixel_shuffle_affine_bwd": [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int,
-                                     c_float, c_void_p, c_int, c_void_p],
-    "pdt_swin_mlp_ok": [c_int, c_int],
-    "pdt_swin_mlp_ws_floats": [c_int],
-    "pdt_swin_mlp_bwd_blocks": [c_int64],
-    "pdt_swin_mlp_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
-                         c_void_p],
-    "pdt_swin_mlp_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                         c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p],
-    "pdt_gemm_ok": [c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int],
-    "pdt_gemm_bf16": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
-                      c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pdt_gemm_stamps_bf16": [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
-                             c_void_p, c_void_p],
-    "pdt_gemm_stamps_epi_bf16": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
-                                 c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pdt_gemm2_bf16": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
-                       c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pdt_syncbn_stats": [c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p],
-    "pdt_syncbn_finalize": [c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pdt_syncbn_elemt": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int,
-                         c_int, c_void_p],
-    "pdt_syncbn_bwd_reduce": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p,
-                              c_void_p],
-    "pdt_syncbn_bwd_elemt": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_int64, c_int, c_int64, c_int, c_int, c_void_p],
-}
+# The bindings are read off the C declarations themselves (csrc/kernels ships with the tree and the library is
+# built from it), so a signature exists in one place only.  Strict on purpose: a C type that is not listed here
+# raises instead of falling through to a default -- a wrong argtype does not fail, it corrupts the argument.
+_KERNEL_SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
+                           "csrc", "kernels")
+_ARG_TYPES = {"hipStream_t": c_void_p, "int": c_int, "int64_t": c_int64, "long long": c_int64, "float": c_float,
+              "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "uint32_t": ctypes.c_uint}
+_RET_TYPES = {"int": c_int, "int64_t": c_int64, "long long": c_int64}
+_DECL = re.compile(r"\bPDT_API\s+([^()]*?)\s*\b(pdt_\w+)\s*\(([^()]*)\)")
 
-_RET64 = {"pdt_swin_mlp_ws_floats", "pdt_narrow_wgrad_ws_floats", "pdt_fp8_gelu_bwd_ws_floats", "pdt_flash_attn_colsum_ws_floats"}
+
+def parse_signatures(texts=None) -> dict:
+    """``{name: (restype, [argtypes])}`` of every ``PDT_API <ret> pdt_<name>(<args>)`` -- prototype or definition --
+    in ``texts`` (default: the ``*.hip`` and ``*.h`` kernel sources).  A name may be declared more than once only
+    with one signature."""
+    if texts is None:
+        texts = []
+        for ext in ("*.hip", "*.h"):
+            for path in sorted(glob.glob(os.path.join(_KERNEL_SRC, ext))):
+                with open(path) as f:
+                    texts.append(f.read())
+    sigs = {}
+    for text in texts:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+        for ret, name, args in _DECL.findall(text):
+            ret = " ".join(ret.split())
+            if ret not in _RET_TYPES:
+                raise TypeError(f"{name}: return type '{ret}' has no ctypes mapping")
+            argtypes = []
+            for arg in ([] if args.strip() in ("", "void") else args.split(",")):
+                if "*" in arg:
+                    argtypes.append(c_void_p)
+                    continue
+                ctype = " ".join([w for w in arg.split() if w != "const"][:-1])     # all but the argument's name
+                if ctype not in _ARG_TYPES:
+                    raise TypeError(f"{name}: argument '{' '.join(arg.split())}' has no ctypes mapping")
+                argtypes.append(_ARG_TYPES[ctype])
+            sig = (_RET_TYPES[ret], argtypes)
+            if sigs.setdefault(name, sig) != sig:
+                raise TypeError(f"{name}: declared twice with different signatures")
+    return sigs
+
 
 F32, BF16, F16, F64 = 0, 1, 2, 3
 
@@ -232,12 +106,12 @@ def load():
                 "(or python -m pytorch_distributedtraining_amd._build)")
             raise _load_error
         lib = ctypes.CDLL(_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, args in _SIGS.items():
+        for name, (restype, argtypes) in parse_signatures().items():
             fn = getattr(lib, name, None)
             if fn is None:
                 continue
-            fn.argtypes = args
-            fn.restype = ctypes.c_int64 if name in _RET64 else c_int
+            fn.argtypes = argtypes
+            fn.restype = restype
         _lib = lib
         return _lib
 

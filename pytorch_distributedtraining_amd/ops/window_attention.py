@@ -94,11 +94,11 @@ class _WindowAttnFn(torch.autograd.Function):
         o = torch.empty((Bw, N, C), dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty((Bw, num_heads, N), dtype=torch.float32, device=qkv.device)
         lib = _lib.require()
-        if qkv.dtype == torch.float32:
-            # fp32 (the reference's precision): exact-f32 MFMA kernels (v_mfma_f32_32x32x2_f32), VALU as fallback
-            ctx.mfma = "f32" if (MFMA_F32 and lib.pdt_win_attn_mfma32_ok(N, num_heads, d)) else None
-        else:
-            ctx.mfma = "bf16" if lib.pdt_win_attn_mfma_ok(N, num_heads, d, _lib.dtype_code(qkv.dtype)) else None
+        dt = _lib.dtype_code(qkv.dtype)
+        # fp32 (the reference's precision): exact-f32 MFMA kernels (v_mfma_f32_32x32x2_f32), VALU as fallback
+        fp32 = qkv.dtype == torch.float32
+        ok = (MFMA_F32 or not fp32) and lib.pdt_win_attn_mfma_ok(N, num_heads, d, dt)
+        ctx.mfma = ("f32" if fp32 else "bf16") if ok else None
         if ctx.mfma:
             # MFMA kernels: dense bias [h, N(q), N(key)] and mask [nw, N, N], no transposed copies
             m = mask.float().contiguous() if mask is not None else None
@@ -115,10 +115,9 @@ class _WindowAttnFn(torch.autograd.Function):
             # O head-major ([Bw, h, N, d]) for a projection that reads it so (ops.linear.linear_from_head_major); the
             # backward then needs the precomputed-delta path (ctx.hm)
             ctx.o_hm = bool(out_head_major) and ctx.hm and ctx.mfma == "bf16"
-            _lib.call("pdt_win_attn_mfma_fwd" if ctx.mfma == "bf16" else "pdt_win_attn_mfma32_fwd", qkv.data_ptr(),
-                      bias.data_ptr(), _lib.ptr(m), _lib.ptr(lab), nw,
+            _lib.call("pdt_win_attn_mfma_fwd", qkv.data_ptr(), bias.data_ptr(), _lib.ptr(m), _lib.ptr(lab), nw,
                       o.data_ptr(), lse.data_ptr(), Bw, N, num_heads, d, float(scale), _lib.ptr(hm), int(given),
-                      int(ctx.o_hm), st)
+                      int(ctx.o_hm), dt, st)
             ctx.save_for_backward(hm if hm is not None else qkv, bias, o, lse)
             ctx.mask = (m, lab, nw)
             ctx.h, ctx.scale, ctx.bias_dtype = num_heads, scale, rel_bias.dtype
@@ -171,10 +170,9 @@ class _WindowAttnFn(torch.autograd.Function):
                 _lib.call("pdt_win_bwd_prep", do.data_ptr(), o.data_ptr(), None if g_hm else g.data_ptr(),
                           delta.data_ptr(), Bw, N, ctx.h, d, _lib.dtype_code(qkv.dtype), int(g_hm), int(ctx.o_hm), st)
                 do = g
-            _lib.call("pdt_win_attn_mfma_bwd" if ctx.mfma == "bf16" else "pdt_win_attn_mfma32_bwd", qkv.data_ptr(),
-                      bias.data_ptr(), _lib.ptr(m), _lib.ptr(lab), nw, o.data_ptr(), do.data_ptr(), lse.data_ptr(),
-                      dqkv.data_ptr(), part.data_ptr(), Bw, N, ctx.h, d, float(ctx.scale), int(ctx.hm),
-                      _lib.ptr(delta), st)
+            _lib.call("pdt_win_attn_mfma_bwd", qkv.data_ptr(), bias.data_ptr(), _lib.ptr(m), _lib.ptr(lab), nw,
+                      o.data_ptr(), do.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), part.data_ptr(), Bw, N, ctx.h, d,
+                      float(ctx.scale), int(ctx.hm), _lib.ptr(delta), _lib.dtype_code(qkv.dtype), st)
             return dqkv, part
         qkv, bias, bias_t, o, lse = ctx.saved_tensors
         m, m_t, nw = ctx.mask
@@ -261,10 +259,9 @@ def head_major_ok(x, N: int, num_heads: int, d: int) -> bool:
     if not (HEAD_MAJOR and x.is_cuda and _lib.available()):
         return False
     dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
-    lib = _lib.require()
-    if dt == torch.bfloat16:
-        return bool(lib.pdt_win_attn_mfma_ok(N, num_heads, d, _lib.dtype_code(dt)))
-    return dt == torch.float32 and MFMA_F32 and bool(lib.pdt_win_attn_mfma32_ok(N, num_heads, d))
+    if dt not in (torch.bfloat16, torch.float32) or (dt == torch.float32 and not MFMA_F32):
+        return False
+    return bool(_lib.require().pdt_win_attn_mfma_ok(N, num_heads, d, _lib.dtype_code(dt)))
 
 
 def supported(qkv, num_heads) -> bool:
@@ -297,8 +294,8 @@ def _perm(src, res, out_shape, H, W, ws, shift, reverse):
         raise TypeError("fused window permutation takes bf16 or fp32 tensors of one dtype")
     out = torch.empty(out_shape, dtype=src.dtype, device=src.device)
     rows = src.numel() // C
-    _lib.call("pdt_window_perm" if src.dtype == torch.bfloat16 else "pdt_window_perm_f32", src.data_ptr(), _lib.ptr(res), out.data_ptr(), rows, C, H, W, ws, shift,
-              1 if reverse else 0, _lib.stream_handle(src.device))
+    _lib.call("pdt_window_perm", src.data_ptr(), _lib.ptr(res), out.data_ptr(), rows, C, H, W, ws, shift,
+              1 if reverse else 0, _lib.dtype_code(src.dtype), _lib.stream_handle(src.device))
     return out
 
 

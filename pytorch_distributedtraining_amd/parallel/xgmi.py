@@ -81,7 +81,7 @@ class XGMIComm:
         self.timeout_us = max(1, min(int(timeout_us), (1 << 32) - 1))
         self.wallclock_khz = int(_lib.require().pdt_xgmi_wallclock_khz())   # s_memrealtime rate (budget unit)
         self.device = torch.device("cuda", torch.cuda.current_device())
-        lib = _lib.require()   # ctypes signatures: ops/_lib.py _SIGS (checked against the C sources)
+        lib = _lib.require()   # ctypes signatures: ops/_lib.py parse_signatures (read off the C sources)
         self._lib = lib
         nbytes = SIG_BYTES + 2 * self.slot_bytes
         own = ctypes.c_void_p()
