@@ -1,4 +1,4 @@
-// Multi-tensor optimizer-side kernels for gfx950: fused AdamW, fused L2-norm / non-finite check,
+// Multi-tensor optimizer-side kernels for gfx950: fused AdamW, fused SGD, fused L2-norm / non-finite check,
 // clip-coefficient, and in-place scale.  One launch covers every tensor in a list.
 //
 // Replaces the per-parameter foreach chain torch runs for the reference's AdamW + clip_grad_norm_
@@ -115,6 +115,104 @@ __global__ __launch_bounds__(MT_THREADS) void adamw_mt_kernel(
       if (O) O[j] = f2bf(p);
     }
   }
+}
+
+struct SgdHyper {
+  float lr, momentum, wd;
+  int nesterov;
+};
+
+// torch/optim/sgd.py _single_tensor_sgd with dampening 0: a zero-initialised buffer reproduces torch's first
+// step (buf = clone(g) == momentum * 0 + g), so there is no step count and a skipped step is exact.
+template <bool MOM>
+__device__ __forceinline__ void sgd_elem(float& p, float& b, float g, const SgdHyper& h) {
+  if (h.wd != 0.f) g += h.wd * p;
+  if (MOM) {
+    b = h.momentum * b + g;
+    g = h.nesterov ? g + h.momentum * b : b;
+  }
+  p -= h.lr * g;
+}
+
+// Same table / block form as adamw_mt_kernel: [param f32, grad, momentum_buffer f32 or null, unused, bf16 out or
+// null, numel].  A null buffer column (momentum == 0) is neither read nor written.
+template <typename G, bool MOM>
+__device__ __forceinline__ void sgd_chunk(const int64_t* __restrict__ mt, int c, int chunk, const SgdHyper& h,
+                                          float gs) {
+  float* __restrict__ P = reinterpret_cast<float*>(mt[0]);
+  const G* __restrict__ Gr = reinterpret_cast<const G*>(mt[1]);
+  float* __restrict__ M = reinterpret_cast<float*>(mt[2]);
+  bf16_t* __restrict__ O = reinterpret_cast<bf16_t*>(mt[4]);
+  const int64_t n = mt[5];
+  const int64_t beg = (int64_t)c * chunk;
+  const int64_t end = beg + chunk < n ? beg + chunk : n;
+  const bool vec_ok = ((mt[0] | mt[1] | mt[2]) & 15) == 0 && (mt[4] & 7) == 0 &&
+                      (sizeof(G) == 4 || (mt[1] & 7) == 0);
+  int64_t i = beg + (int64_t)threadIdx.x * 4;
+  if (vec_ok) {
+    for (; i + 3 < end; i += MT_THREADS * 4) {
+      f32x4 p = *reinterpret_cast<f32x4*>(P + i);
+      f32x4 m = {0.f, 0.f, 0.f, 0.f};
+      if (MOM) m = *reinterpret_cast<f32x4*>(M + i);
+      float g[4];
+      if constexpr (sizeof(G) == 4) {
+        f32x4 gg = *reinterpret_cast<const f32x4*>(Gr + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = gg[k];
+      } else {
+        u16x4 gg = *reinterpret_cast<const u16x4*>(Gr + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = bf2f(gg[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float pk = p[k], mk = m[k];
+        sgd_elem<MOM>(pk, mk, g[k] * gs, h);
+        p[k] = pk; m[k] = mk;
+      }
+      *reinterpret_cast<f32x4*>(P + i) = p;
+      if (MOM) *reinterpret_cast<f32x4*>(M + i) = m;
+      if (O) {
+        u16x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = f2bf(p[k]);
+        *reinterpret_cast<u16x4*>(O + i) = o;
+      }
+    }
+    // tail (fewer than 4 left for this thread)
+    for (; i < end; ++i) {
+      float p = P[i], m = MOM ? M[i] : 0.f;
+      sgd_elem<MOM>(p, m, to_f<G>(Gr[i]) * gs, h);
+      P[i] = p;
+      if (MOM) M[i] = m;
+      if (O) O[i] = f2bf(p);
+    }
+  } else {
+    for (int64_t j = beg + threadIdx.x; j < end; j += MT_THREADS) {
+      float p = P[j], m = MOM ? M[j] : 0.f;
+      sgd_elem<MOM>(p, m, to_f<G>(Gr[j]) * gs, h);
+      P[j] = p;
+      if (MOM) M[j] = m;
+      if (O) O[j] = f2bf(p);
+    }
+  }
+}
+
+// Fused SGD (momentum / Nesterov, L2 weight decay).  lr_ptr: the learning rate read from the device, so a
+// captured step follows a schedule that fills the tensor in place.
+template <typename G>
+__global__ __launch_bounds__(MT_THREADS) void sgd_mt_kernel(
+    const int64_t* __restrict__ meta, const int* __restrict__ blk, int chunk, SgdHyper h,
+    const float* __restrict__ gscale, const int* __restrict__ found_inf, const float* __restrict__ lr_ptr) {
+  if (found_inf != nullptr && *found_inf != 0) return;  // GradScaler semantics: skip the step
+  const float gs = gscale ? *gscale : 1.f;
+  if (lr_ptr != nullptr) h.lr = *lr_ptr;
+  const int t = blk[2 * blockIdx.x], c = blk[2 * blockIdx.x + 1];
+  const int64_t* mt = meta + (int64_t)t * MT_META;
+  if (h.momentum != 0.f && mt[2] != 0)
+    sgd_chunk<G, true>(mt, c, chunk, h, gs);
+  else
+    sgd_chunk<G, false>(mt, c, chunk, h, gs);
 }
 
 // Sum of squares per block (ptr0 of each tensor), written to partial[blockIdx.x].
@@ -257,6 +355,21 @@ PDT_API int pdt_adamw_mt(const int64_t* meta, const int* blk, int nblocks, int c
     adamw_mt_kernel<float><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, dstep);
   else
     adamw_mt_kernel<bf16_t><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, dstep);
+  return (int)hipGetLastError();
+}
+
+// lr_ptr (device, nullable) overrides lr; a non-zero momentum needs the buffer column of every row set
+PDT_API int pdt_sgd_mt(const int64_t* meta, const int* blk, int nblocks, int chunk, int grad_dtype, float lr,
+                       float momentum, float wd, int nesterov, const float* gscale, const int* found_inf,
+                       const float* lr_ptr, hipStream_t stream) {
+  SgdHyper h{lr, momentum, wd, nesterov};
+  if (nblocks <= 0) return 0;
+  if (grad_dtype == kF32)
+    sgd_mt_kernel<float><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, lr_ptr);
+  else if (grad_dtype == kBF16)
+    sgd_mt_kernel<bf16_t><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, lr_ptr);
+  else
+    return (int)hipErrorInvalidValue;
   return (int)hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-"""Multi-tensor launches: fused AdamW, fused L2 norm (+ non-finite check), clip coefficient, scale.
+"""Multi-tensor launches: fused AdamW, fused SGD, fused L2 norm (+ non-finite check), clip coefficient, scale.
 
 One HIP launch covers an arbitrary list of tensors through a device-resident table
 (``csrc/kernels/multi_tensor.hip``).  The engines keep parameters/gradients in flat buffers so their
@@ -246,6 +246,64 @@ def adamw_step(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float,
               _lib.dtype_code(gdt), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
               float(step_size), float(bc2_sqrt), 1 if decoupled else 0, _lib.ptr(grad_scale), _lib.ptr(found_inf),
               _lib.ptr(dstep), _lib.stream_handle(dev))
+
+
+def sgd_step(params, grads, bufs, *, lr, momentum: float, weight_decay: float, nesterov: bool,
+             grad_scale: torch.Tensor | None = None, found_inf: torch.Tensor | None = None, out_bf16=None,
+             table: TensorTable | None = None) -> None:
+    """One fused (multi-tensor) SGD update, torch.optim.SGD's math with dampening 0 (torch/optim/sgd.py
+    ``_single_tensor_sgd``).  fp32 params / momentum buffers; grads fp32 or bf16.
+
+    lr: a float, or a 1-element fp32 tensor on the parameters' device -- the kernel then reads the rate from the
+    device, so a launch captured into a HIP graph follows a schedule that ``fill_``s the tensor.
+    bufs: the momentum buffers (zeros before the first step); ignored, and may be None, when ``momentum`` is 0.
+    grad_scale / found_inf / out_bf16 / table: as in ``adamw_step``."""
+    if len(params) == 0:
+        return
+    dev = params[0].device
+    use_mom = momentum != 0
+    if use_mom:
+        assert bufs is not None and len(bufs) == len(params) and all(b is not None for b in bufs), \
+            "sgd_step: momentum != 0 needs a buffer per parameter"
+    if dev.type != "cuda":
+        if found_inf is not None and int(found_inf.reshape(-1)[0]) != 0:
+            return
+        gs = None if grad_scale is None else grad_scale.reshape(())
+        rate = lr.reshape(()).to(torch.float32) if torch.is_tensor(lr) else float(lr)
+        for i, p in enumerate(params):
+            g = grads[i].float()
+            if gs is not None:
+                g = g * gs
+            if weight_decay != 0:
+                g = g + weight_decay * p
+            if use_mom:
+                b = bufs[i]
+                b.mul_(momentum).add_(g)
+                g = g.add(b, alpha=momentum) if nesterov else b
+            if torch.is_tensor(rate):
+                p.sub_(g * rate)
+            else:
+                p.add_(g, alpha=-rate)
+            if out_bf16 is not None and out_bf16[i] is not None:
+                out_bf16[i].copy_(p)
+        return
+    gdt = grads[0].dtype
+    if gdt not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"sgd_step: gradients must be fp32 or bf16, got {gdt}")
+    if torch.is_tensor(lr):
+        if lr.dtype != torch.float32 or lr.numel() != 1 or lr.device != dev:
+            raise TypeError("sgd_step: a tensor lr must be one fp32 element on the parameters' device")
+        lr_ptr, lr_val = lr.data_ptr(), 0.0
+    else:
+        lr_ptr, lr_val = 0, float(lr)
+    if table is None:
+        none = [None] * len(params)
+        cols = [list(params), list(grads), list(bufs) if use_mom else none, none,
+                list(out_bf16) if out_bf16 is not None else none]
+        table = _cache.get(("sgd", gdt, len(params), id(params[0])), cols)
+    _lib.call("pdt_sgd_mt", table.meta.data_ptr(), table.blk.data_ptr(), table.nblocks, table.chunk,
+              _lib.dtype_code(gdt), lr_val, float(momentum), float(weight_decay), 1 if nesterov else 0,
+              _lib.ptr(grad_scale), _lib.ptr(found_inf), lr_ptr, _lib.stream_handle(dev))
 
 
 def step_inc_(dstep: torch.Tensor, found_inf: torch.Tensor | None = None) -> None:

@@ -22,30 +22,15 @@ and Fairscale-DDP.py:78-86; math order torch/optim/adam.py:419-547.
 from __future__ import annotations
 
 import torch
-from torch.optim import Optimizer
 
 from ..ops import multi_tensor as mt
-from ..ops.multi_tensor import _dense
+from ._fused import FusedOptimizer, _like, _same_layout  # noqa: F401
 from ._grads import grad_of
 
 
-def _same_layout(g, p) -> bool:
-    """Same element order in memory: strides equal wherever the size is not 1 (a size-1 dimension's stride is
-    arbitrary -- a contiguous [Cout, Cin, 1, 1] gradient of a channels_last 1x1-conv weight is already in its order,
-    and autograd's layout contract accepts it as is)."""
-    return g.shape == p.shape and all(gs == ps for gs, ps, n in zip(g.stride(), p.stride(), p.shape) if n != 1)
+class FusedAdamW(FusedOptimizer):
+    _label = "FusedAdamW"
 
-
-def _like(g, p):
-    """The gradient in the parameter's memory layout (the kernel walks storage linearly)."""
-    if p.dim() <= 1:
-        return g if g.is_contiguous() else g.contiguous()
-    if _same_layout(g, p) and _dense(g):
-        return g
-    return torch.empty_like(p, dtype=g.dtype).copy_(g)
-
-
-class FusedAdamW(Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
                  decoupled=True, capturable=False, **_ignored):
         if amsgrad:
@@ -54,7 +39,6 @@ class FusedAdamW(Optimizer):
                         maximize=False, foreach=None, capturable=capturable, differentiable=False, fused=None,
                         decoupled=decoupled)
         super().__init__(params, defaults)
-        self._tables = mt.TableCache()
         self._dsteps: dict = {}
 
     def _counters(self, present):
@@ -100,64 +84,9 @@ class FusedAdamW(Optimizer):
             out.append((c, ps))
         return out
 
-    def zero_grad(self, set_to_none: bool = True):
-        """torch semantics for ``.grad``, except for engine-owned flat gradients: DDP's compute-dtype masters
-        (``_pdt_zero_grad``) and parameters whose ``.grad`` is still a view of a DDP bucket flat
-        (``_pdt_grad_flat``) get their flat zeroed in place -- ONE fill per flat instead of a None per
-        parameter that the next forward would re-attach view by view (ResNet-50: 161 views, a host gap at
-        every step start).  Those gradients therefore read as zeros, not None, after ``set_to_none=True`` (as
-        with torch DDP's ``gradient_as_bucket_view``, whose views stay attached to the bucket).  A flat is filled
-        whole only when every parameter viewing it (``_pdt_grad_members``) belongs to THIS optimizer; otherwise
-        only this optimizer's own views are zeroed, so another optimizer stepping the same bucket later still
-        sees its gradients."""
-        mine = {id(p) for group in self.param_groups for p in group["params"]}
-        flats, views, rest, owned = {}, [], [], {}
-        for group in self.param_groups:
-            for p in group["params"]:
-                zero = getattr(p, "_pdt_zero_grad", None)
-                if zero is not None:
-                    flats[id(zero)] = zero
-                    continue
-                g = p.grad
-                if g is None:
-                    continue
-                f = getattr(p, "_pdt_grad_flat", None)
-                if f is not None and g._base is f:
-                    ok = owned.get(id(f))
-                    if ok is None:
-                        members = getattr(p, "_pdt_grad_members", None)
-                        ok = owned[id(f)] = members is not None and all(id(q) in mine for q in members)
-                    if ok:
-                        flats[id(f)] = f.zero_
-                    else:
-                        views.append(g)      # keep the view attached: the bucket reduction reads it in place
-                    continue
-                rest.append(p)
-        for zero in flats.values():
-            if getattr(zero, "_pdt_set_to_none", False):
-                zero(set_to_none)      # an engine that keeps per-parameter gradients (DDP._steal_grads)
-            else:
-                zero()
-        if views:
-            torch._foreach_zero_(views)
-        if set_to_none:
-            for p in rest:
-                p.grad = None
-        elif rest:
-            grads = []
-            for p in rest:
-                if p.grad.grad_fn is not None:
-                    p.grad.detach_()
-                else:
-                    p.grad.requires_grad_(False)
-                grads.append(p.grad)
-            torch._foreach_zero_(grads)
-
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._dsteps.clear()     # device step counters are rebuilt from the loaded per-parameter steps
-        for p in self.state:
-            p._pdt_opt_state = True   # engines must not re-lay-out this parameter any more (DDP rebuild)
 
     def _init_state(self, p):
         st = self.state[p]
@@ -191,17 +120,7 @@ class FusedAdamW(Optimizer):
                 id(self.state[p].get("step")) in self._dsteps for p in group["params"] if p in self.state)
             if found_inf is not None and found_inf.device.type != "cuda" and int(found_inf.reshape(-1)[0]) != 0:
                 continue
-            present = []
-            for p in group["params"]:
-                g = grad_of(p)
-                if g is None:
-                    continue
-                if g.is_sparse:
-                    raise RuntimeError("FusedAdamW does not support sparse gradients")
-                if p.dtype != torch.float32:
-                    raise TypeError("FusedAdamW keeps fp32 master params; wrap low-precision models with an "
-                                    "engine (FSDP/ZeRO) or keep params fp32 and use autocast")
-                present.append(p)
+            present = self._present(group)
             counters = {}
             if dev_step:
                 for c, ps in self._counters(present):
@@ -221,11 +140,7 @@ class FusedAdamW(Optimizer):
                 grads = [_like(grad_of(p), p) for p in ps]
                 ms = [self.state[p]["exp_avg"] for p in ps]
                 vs = [self.state[p]["exp_avg_sq"] for p in ps]
-                lps = [getattr(p, "_pdt_lp_shard", None) for p in ps]
-                # the kernel's epilogue writes bf16 compute copies; an fp32 "copy" (a DDP compute-copy model's
-                # batch-norm group) is refreshed by a plain copy after the step
-                lp_other = [(p, x) for p, x in zip(ps, lps) if x is not None and x.dtype != torch.bfloat16]
-                lps = [x if (x is not None and x.dtype == torch.bfloat16) else None for x in lps]
+                lps, lp_other = self._compute_copies(ps)
                 has_lp = any(x is not None for x in lps)
                 table = None
                 if dev.type == "cuda":
@@ -237,12 +152,7 @@ class FusedAdamW(Optimizer):
                               weight_decay=group["weight_decay"], step=max(step, 1),
                               decoupled=group.get("decoupled", True), grad_scale=grad_scale, found_inf=found_inf,
                               out_bf16=lps if has_lp else None, table=table, dstep=dstep)
-                with torch.no_grad():
-                    for p, x in lp_other:
-                        x.copy_(p)
-                for p in ps:
-                    if getattr(p, "_pdt_lp_shard", None) is not None:
-                        p._pdt_lp_version = p._version   # compute copy already refreshed by the kernel
+                self._refresh_copies(ps, lp_other)
             if buckets:
                 # tables of this group's counters that no longer exist (a split counter, a reloaded checkpoint)
                 # are dropped, so their device tables do not pile up over a long run

@@ -10,7 +10,7 @@ MI355X-first design:
     large -- 64 MiB default, chosen by arithmetic so a ring step per xGMI link would stay bandwidth- rather
     than latency-bound; a default, unmeasured on a multi-GPU node), and the model parameters, their gradients (``gradient_as_bucket_view``: autograd
     accumulates straight into the bucket, no copy-in) and -- with ``compute_dtype`` -- the fp32 master
-    copy all share that layout.  The optimizer then updates the whole model with ONE fused AdamW
+    copy all share that layout.  The optimizer then updates the whole model with ONE fused optimizer
     launch reading bf16 grads and writing the bf16 compute params in its epilogue.
   * Readiness is tracked by the native ``ReadyTracker``; buckets are released strictly in order and
     all-reduced (AVG, fused averaging inside RCCL) asynchronously on the RCCL stream while backward
@@ -162,7 +162,7 @@ class _FlatGroup:
             o = self.offset_of[li]
             # same strides as the parameter (channels_last convs): autograd accumulates in place
             p.grad = _pview(self.flat_grad, p, o)
-            p._pdt_grad_flat = self.flat_grad   # FusedAdamW.zero_grad zeroes the flat once, views stay attached
+            p._pdt_grad_flat = self.flat_grad   # FusedOptimizer.zero_grad zeroes the flat once, views stay attached
             p._pdt_grad_members = self.params   # ... when one optimizer owns every parameter viewing it
 
 

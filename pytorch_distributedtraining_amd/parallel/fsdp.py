@@ -5,7 +5,7 @@ Design (MI355X-first, not a port of torch FSDP):
     ``FlatLayout`` planner (16-element aligned, padded to a multiple of world_size) into
       - ``flat_param``: the fp32 MASTER shard (an nn.Parameter -- what the optimizer steps),
       - ``lp_shard``:   the bf16 compute copy of the shard (all-gather input, refreshed by the fused
-                        AdamW epilogue, so no separate cast pass),
+                        optimizer's epilogue, so no separate cast pass),
       - ``full``:       the bf16 gathered buffer; its storage is released after forward
                         (FULL_SHARD) and re-gathered before backward.
     The original parameters are replaced by views into ``full`` -- the outputs of ONE autograd node per unit
@@ -301,7 +301,7 @@ class FullyShardedDataParallel(nn.Module):
         comm: collective layer (default: the initialised default process group).
         forward_prefetch / backward_prefetch: overlap the next unit's all-gather with compute.
         keep_low_precision_grads: leave the reduced shard gradient in ``reduce_dtype`` as
-            ``flat_param._pdt_grad`` (read by FusedAdamW / clip_grad_norm_) instead of materialising an
+            ``flat_param._pdt_grad`` (read by the fused optimizers / clip_grad_norm_) instead of materialising an
             fp32 ``.grad`` -- use with the framework's fused optimizer.
         accumulate: "sharded" (default) or "local" -- gradient accumulation under ``no_sync`` (module docstring).
     """

@@ -16,10 +16,10 @@ MI355X-first design (not Fairscale's per-rank broadcasts and per-parameter reduc
     views into it, so the post-step exchange is ONE all-gather of the owners' segments (world_size
     broadcasts before), and a rank's optimizer state / fp32 master / gradient shard is one contiguous
     slice.
-  * ``broadcast_fp16``: the all-gather payload is a bf16 (fp16 on CPU) flat; the fused AdamW writes the
-    owner's slice of it in its epilogue (no cast pass), receivers cast only the peers' slices back.
+  * ``broadcast_fp16``: the all-gather payload is a bf16 (fp16 on CPU) flat; the fused optimizer (AdamW, SGD)
+    writes the owner's slice of it in its epilogue (no cast pass), receivers cast only the peers' slices back.
   * ``compute_dtype=torch.bfloat16``: the module itself runs on bf16 parameters (views of the bf16 flat)
-    while each rank keeps fp32 masters for its OWN segment only; the fused AdamW updates the masters and
+    while each rank keeps fp32 masters for its OWN segment only; the fused optimizer updates the masters and
     writes the bf16 parameters in its epilogue, the all-gather then moves bf16.  No per-forward fp32->bf16
     weight casts and no bf16->fp32 gradient casts (the autocast "cast storm").
   * ``ShardedDataParallel`` (ZeRO-2, ``reduce_mode="reduce"``): a rank keeps a persistent gradient buffer
@@ -29,8 +29,8 @@ MI355X-first design (not Fairscale's per-rank broadcasts and per-parameter reduc
     asynchronously from the grad hooks, and freed -- per-rank gradient memory is ~1/world of the model.
     ``reduce_mode="all_reduce"`` is the ZeRO-1 gradient path (DDP + OSS): full gradients, bucketed
     all-reduces over the same flat.
-  * Optimizer-state consolidation gathers flat per-key state slices (tensors, no pickled state), plus one
-    tiny all-reduce of the per-parameter step counts.
+  * Optimizer-state consolidation gathers flat per-key state slices (tensors, no pickled state), plus tiny
+    all-reduces of the per-parameter step counts.
 """
 from __future__ import annotations
 
@@ -84,17 +84,19 @@ class OSS(Optimizer):
 
     def __init__(self, params, optim=None, comm: Comm | None = None, broadcast_fp16: bool = False, group=None,
                  compute_dtype: torch.dtype | None = None, **defaults):
-        from ..optim import FusedAdamW
+        from ..optim import FusedAdamW, FusedOptimizer
 
         self.comm = comm or (Comm(group) if group is not None else default_comm())
         self.optim_cls = optim or FusedAdamW
         self.broadcast_fp16 = broadcast_fp16
         self.compute_dtype = compute_dtype
-        if compute_dtype is not None and not issubclass(self.optim_cls, FusedAdamW):
-            # the fp32 masters read their gradient through _pdt_grad_src, which only FusedAdamW follows: a
+        if compute_dtype is not None and not (isinstance(self.optim_cls, type) and
+                                              issubclass(self.optim_cls, FusedOptimizer)):
+            # the fp32 masters read their gradient through _pdt_grad_src, which only a FusedOptimizer follows: a
             # torch optimizer would see master.grad None and silently never update anything
-            raise ValueError("OSS(compute_dtype=...) needs optim=FusedAdamW (the fp32 masters' gradients are "
-                             f"the compute-dtype module gradients), got {self.optim_cls.__name__}")
+            raise ValueError("OSS(compute_dtype=...) needs a fused optimizer (FusedAdamW, FusedSGD: the fp32 "
+                             "masters' gradients are the compute-dtype module gradients), got "
+                             f"{getattr(self.optim_cls, '__name__', self.optim_cls)}")
         super().__init__(params, defaults)
         world, rank = self.comm.world_size, self.comm.rank
         self._all_params = [p for g in self.param_groups for p in g["params"]]
@@ -114,7 +116,7 @@ class OSS(Optimizer):
         self._local_group_idx = [i for i, g in enumerate(local_groups) if g["params"]]
         nonempty = [g for g in local_groups if g["params"]]
         self.optim = self.optim_cls(nonempty, **defaults) if nonempty else None
-        self._fused = isinstance(self.optim, FusedAdamW)
+        self._fused = isinstance(self.optim, FusedOptimizer)
         self._state_cache = None
 
     # ---------------------------------------------------------------- layout
@@ -150,7 +152,7 @@ class OSS(Optimizer):
                                       device=dev)
                 for li, p in enumerate(ps):
                     if bank.owners[li] == rank:
-                        p._pdt_lp_shard = bank.view(bank.lp, li)   # AdamW epilogue writes the payload
+                        p._pdt_lp_shard = bank.view(bank.lp, li)   # optimizer epilogue writes the payload
                 # The epilogue only rewrites what it steps: a frozen / gradient-less parameter or a skipped
                 # (found_inf) step leaves the owner's slice as is, so it must hold the current values from
                 # the start -- never zeros that the all-gather would spread to every peer.
@@ -291,6 +293,7 @@ class OSS(Optimizer):
         n = len(self._all_params)
         steps = torch.zeros(n, dtype=torch.float64, device=dev)
         has = torch.zeros(n, dtype=torch.float64, device=dev)
+        counted = torch.zeros(n, dtype=torch.float64, device=dev)   # state with a step count (none under SGD)
         full = {}
         for bank in self._banks:
             for k in keys:
@@ -308,22 +311,25 @@ class OSS(Optimizer):
             for li, p in enumerate(bank.params):
                 if bank.owners[li] == rank and self.optim is not None:
                     st = self.optim.state.get(self._opt_param(p))
-                    if st and "step" in st:
-                        steps[bank.idxs[li]] = float(st["step"])
+                    if st:
                         has[bank.idxs[li]] = 1.0
+                        if "step" in st:
+                            steps[bank.idxs[li]] = float(st["step"])
+                            counted[bank.idxs[li]] = 1.0
         self.comm.all_reduce(steps, "sum")
         self.comm.all_reduce(has, "sum")
+        self.comm.all_reduce(counted, "sum")
         if rank != recipient_rank:
             self._state_cache = None
             return
-        steps, has = steps.cpu(), has.cpu()
+        steps, has, counted = steps.cpu(), has.cpu(), counted.cpu()
         state = {}
         for bank in self._banks:
             for li, p in enumerate(bank.params):
                 gi = bank.idxs[li]
                 if not has[gi]:
                     continue
-                ent = {"step": torch.tensor(float(steps[gi]))}
+                ent = {"step": torch.tensor(float(steps[gi]))} if counted[gi] else {}
                 for k in keys:
                     ent[k] = bank.view(full[(id(bank), k)], li).detach().to("cpu", copy=True).view(p.shape)
                 state[gi] = ent

@@ -3,8 +3,8 @@ BASELINE.json configs" + "env overrides for comm tuning").
 
 A ``RunConfig`` names the model, the engine combination (the reference's Stoke flags: distributed /
 fairscale_oss / fairscale_sddp, plus fsdp), precision, batch / accumulation / clipping (Stoke-DDP.py:159,
-247-253), optimizer kwargs (Stoke-DDP.py:226-235) and the DDP bucket sizing.  ``load_config`` reads YAML
-(safe loader) or JSON; ``apply_env_overrides`` lets a launcher retune communication without editing files:
+247-253), optimizer (``name: adamw | sgd`` + its kwargs, Stoke-DDP.py:226-235) and the DDP bucket sizing.
+``load_config`` reads YAML (safe loader) or JSON; ``apply_env_overrides`` lets a launcher retune communication without editing files:
 
     PDT_BUCKET_MB, PDT_FIRST_BUCKET_MB   DDP bucket cap / first bucket (MiB)
     PDT_XGMI=1|auto, PDT_XGMI_ONESHOT_KB route eligible collectives through the xGMI peer kernels (auto: by
@@ -71,9 +71,23 @@ def load_config(path: str, **overrides) -> RunConfig:
     unknown = set(data) - names
     if unknown:
         raise ValueError(f"{path}: unknown config keys {sorted(unknown)}")
-    if "optimizer" in data and "betas" in data["optimizer"]:
-        data["optimizer"] = dict(data["optimizer"], betas=tuple(data["optimizer"]["betas"]))
+    if "optimizer" in data:
+        optimizer_name(data["optimizer"])                       # an unknown name fails here, not at the first step
+        if "betas" in data["optimizer"]:
+            data["optimizer"] = dict(data["optimizer"], betas=tuple(data["optimizer"]["betas"]))
     return RunConfig(**data)
+
+
+OPTIMIZERS = ("adamw", "sgd")
+
+
+def optimizer_name(optimizer: Dict[str, Any]) -> str:
+    """The optional ``name`` of an optimizer dict (``adamw`` by default, or ``sgd``); the other keys are the
+    optimizer's keyword arguments."""
+    name = str(optimizer.get("name", "adamw")).lower()
+    if name not in OPTIMIZERS:
+        raise ValueError(f"unknown optimizer name '{optimizer.get('name')}' (one of {', '.join(OPTIMIZERS)})")
+    return name
 
 
 def apply_env_overrides(cfg: RunConfig, env=None) -> RunConfig:

@@ -23,7 +23,7 @@ import time
 import torch
 import torch.nn.functional as F
 
-from .run_config import RunConfig, apply_env_overrides, load_config
+from .run_config import RunConfig, apply_env_overrides, load_config, optimizer_name
 
 
 def build_model(cfg: RunConfig):
@@ -76,7 +76,9 @@ def loss_fn(cfg: RunConfig, kind: str):
     return lambda out, tgt: F.mse_loss(out.float(), tgt)
 
 
-def run(cfg: RunConfig) -> dict:
+def run(cfg: RunConfig, optimizer_cls=None) -> dict:
+    """``optimizer_cls``: an optimizer class to use instead of the one ``cfg.optimizer`` names (a subclass of a torch
+    optimizer is never mapped to its fused equivalent: the A/B baseline of the fused optimizers)."""
     from .trainer import ClipGradNormConfig, DDPConfig, FairscaleFSDPConfig, StokeOptimizer, Trainer
     from .utils.logging import MetricsSink, ThroughputMeter
     from .utils.profiling import StepTimer
@@ -94,7 +96,10 @@ def run(cfg: RunConfig) -> dict:
     configs = [ddp_cfg, FairscaleFSDPConfig(activation_checkpointing=cfg.activation_checkpointing)]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     distributed = cfg.distributed if (world > 1 or cfg.distributed == "fsdp") else None
-    opt = StokeOptimizer(optimizer=torch.optim.AdamW, optimizer_kwargs=dict(cfg.optimizer))
+    opt_kw = dict(cfg.optimizer)
+    opt_kw.pop("name", None)
+    opt_cls = optimizer_cls or {"adamw": torch.optim.AdamW, "sgd": torch.optim.SGD}[optimizer_name(cfg.optimizer)]
+    opt = StokeOptimizer(optimizer=opt_cls, optimizer_kwargs=opt_kw)
     precision = None if cfg.precision == "fp32" else "bf16" if cfg.precision == "fp8" else cfg.precision
     tr = Trainer(model, optimizer=opt, loss=loss_fn(cfg, kind), batch_size_per_device=cfg.batch_size_per_device,
                  grad_accum_steps=cfg.grad_accum_steps,

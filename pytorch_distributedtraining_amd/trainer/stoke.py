@@ -10,7 +10,7 @@ Same method names and semantics as the reference exercises them:
   ``no_sync()`` on non-boundary micro-steps; ``step()`` acts only on accumulation boundaries:
   (unscale ->) clip -> optimizer step -> zero grads.  effective batch = per-device x accum x world.
 * MI355X-first execution underneath: RCCL engines from ``parallel`` (bucketed DDP, ZeRO-1 OSS,
-  ZeRO-2 ShardedDDP, FSDP), the fused AdamW and fused clip/unscale kernels (gradient multiplier and
+  ZeRO-2 ShardedDDP, FSDP), the fused AdamW / SGD and fused clip/unscale kernels (gradient multiplier and
   found_inf stay on device -- no host sync between backward and update), bf16 autocast by default,
   loss/EMA synchronisation only when printed.
 """
@@ -26,7 +26,7 @@ import torch.nn as nn
 from ..data.loader import DeviceDataLoader
 from ..ops import picks
 from ..ops.fp8 import fp8_autocast
-from ..optim import FusedAdamW, GradScaler, clip_grad_norm_
+from ..optim import FusedAdamW, FusedOptimizer, FusedSGD, GradScaler, clip_grad_norm_
 from ..optim._grads import grad_of
 from ..parallel.comm import Comm
 from ..utils import checkpoint as ckpt
@@ -223,6 +223,7 @@ class Trainer:
         opt_spec = optimizer if isinstance(optimizer, StokeOptimizer) else StokeOptimizer(**optimizer) \
             if isinstance(optimizer, dict) else StokeOptimizer(optimizer)
         opt_cls = self._fused_equivalent(opt_spec.optimizer)
+        fused_cls = isinstance(opt_cls, type) and issubclass(opt_cls, FusedOptimizer)
         kw = dict(opt_spec.optimizer_kwargs)
         self._sharded_grads = False
         self.compute_dtype = None
@@ -237,16 +238,16 @@ class Trainer:
                 model.to(self.device), wrap_classes=c.wrap_classes or None,
                 sharding_strategy=ShardingStrategy(c.sharding_strategy), mixed_precision=mp, comm=self.comm,
                 device=self.device, forward_prefetch=c.forward_prefetch, backward_prefetch=c.backward_prefetch,
-                keep_low_precision_grads=opt_cls is FusedAdamW)
+                keep_low_precision_grads=fused_cls)
             self._optimizer = opt_cls(self._engine.flat_parameters(), **kw)
             self._clip_params = self._engine.flat_parameters
             self._sharded_grads = True
         else:
             model.to(self.device)
             # bf16 compute copy: with the fused optimizer the module itself runs on bf16 parameters that the
-            # AdamW epilogue rewrites from fp32 masters, instead of autocast casting every fp32 weight to bf16
+            # optimizer epilogue rewrites from fp32 masters, instead of autocast casting every fp32 weight to bf16
             # in every forward and every bf16 gradient back to fp32 (thousands of cast kernels per step)
-            cdt = torch.bfloat16 if (self.gpu and self.fp16 == "bf16" and opt_cls is FusedAdamW) else None
+            cdt = torch.bfloat16 if (self.gpu and self.fp16 == "bf16" and fused_cls) else None
             self.compute_dtype = cdt
             if fairscale_oss:
                 from ..parallel.zero import OSS, ShardedDataParallel
@@ -294,9 +295,12 @@ class Trainer:
 
     # ------------------------------------------------------------------ construction helpers
     def _fused_equivalent(self, cls):
-        """torch AdamW/Adam -> the framework's fused AdamW on GPU (identical math and state layout)."""
+        """torch AdamW / Adam / SGD -> the framework's fused AdamW / SGD on GPU (identical math and state layout).
+        A subclass of a torch optimizer is the user's own and stays as given."""
         if self.gpu and cls in (torch.optim.AdamW, FusedAdamW):
             return FusedAdamW
+        if self.gpu and cls in (torch.optim.SGD, FusedSGD):
+            return FusedSGD
         if self.gpu and cls is torch.optim.Adam:
             return lambda params, **kw: FusedAdamW(params, decoupled=False, **kw)
         return cls
@@ -408,8 +412,7 @@ class Trainer:
     def _step(self):
         params = self._clip_params() if callable(self._clip_params) else self._clip_params
         opt = self._optimizer
-        fused = isinstance(opt, FusedAdamW) or (hasattr(opt, "optim") and isinstance(getattr(opt, "optim", None),
-                                                                                    FusedAdamW))
+        fused = isinstance(opt, FusedOptimizer) or isinstance(getattr(opt, "optim", None), FusedOptimizer)
         inv_scale = 1.0 / self.scaler.get_scale() if self.scaler is not None else 1.0
         max_norm = self.grad_clip.max_norm if isinstance(self.grad_clip, ClipGradNormConfig) else 0.0
         norm_type = self.grad_clip.norm_type if isinstance(self.grad_clip, ClipGradNormConfig) else 2.0
@@ -444,17 +447,17 @@ class Trainer:
         buffers and replays the graph, advancing the Trainer's step counters exactly as the eager call does.
         Removes the per-launch host cost of many-small-kernel steps (SwinIR: ~3,500 launches per step).
 
-        Needs the fused optimizer (switched to its capturable device step count here; under OSS the wrapped
-        one) and no fp16 GradScaler (its scale update is host logic).  At world > 1 the collectives are
+        Needs a fused optimizer (FusedAdamW is switched to its capturable device step count here; under OSS the
+        wrapped one) and no fp16 GradScaler (its scale update is host logic).  At world > 1 the collectives are
         captured with the step: RCCL (``nccl``) process group, DDP or ShardedDDP engine (their bucket
         readiness is switched to capture-safe hooks: ``prepare_capture``), and the xGMI mesh is bypassed
         while capturing (its epochs are host arguments).  FSDP's unit hooks are not capture-safe."""
         from ..utils.graphs import GraphedStep
         opt = self._optimizer
-        inner = opt.optim if isinstance(getattr(opt, "optim", None), FusedAdamW) else opt
-        fused = isinstance(inner, FusedAdamW)
+        inner = opt.optim if isinstance(getattr(opt, "optim", None), FusedOptimizer) else opt
+        fused = isinstance(inner, FusedOptimizer)
         if not (self.gpu and fused and self.scaler is None):
-            raise RuntimeError("Trainer.graph needs a GPU, FusedAdamW and no fp16 GradScaler")
+            raise RuntimeError("Trainer.graph needs a GPU, a fused optimizer and no fp16 GradScaler")
         if self.world_size_ > 1:
             if self.comm.backend != "nccl" or not hasattr(self._engine, "prepare_capture"):
                 raise RuntimeError("Trainer.graph at world > 1 needs the RCCL (nccl) backend and a DDP or "

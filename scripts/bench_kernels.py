@@ -107,6 +107,25 @@ def adamw(n=164_000_000):
     report(f"adamw flat {n/1e6:.0f}M (bf16 grad, bf16 copy-out)", ms, timeit(ref, iters=10), bytes_=n * (12 + 2 + 12 + 2))
 
 
+def sgd(n=164_000_000):
+    """Nesterov SGD on the same flat as ``adamw`` (bf16 gradient, bf16 copy-out) vs torch.optim.SGD(foreach=True)'s
+    functional form plus the cast of the updated parameters."""
+    from pytorch_distributedtraining_amd.ops import sgd_step
+    from torch.optim.sgd import sgd as torch_sgd
+    p, m = (torch.randn(n, device="cuda") for _ in range(2))
+    g = torch.randn(n, device="cuda", dtype=torch.bfloat16)
+    lp = torch.empty(n, device="cuda", dtype=torch.bfloat16)
+    ms = timeit(lambda: sgd_step([p], [g], [m], lr=1e-4, momentum=0.9, weight_decay=1e-4, nesterov=True,
+                                 out_bf16=[lp]), iters=10)
+    gf = g.float()
+
+    def ref():
+        torch_sgd([p], [gf], [m], foreach=True, weight_decay=1e-4, momentum=0.9, lr=1e-4, dampening=0.0,
+                  nesterov=True, maximize=False)
+        lp.copy_(p)
+    report(f"sgd flat {n/1e6:.0f}M (bf16 grad, bf16 copy-out)", ms, timeit(ref, iters=10), bytes_=n * (8 + 8 + 2 + 2))
+
+
 def cross_entropy(rows=8192, V=50304):
     from pytorch_distributedtraining_amd.ops import cross_entropy as ce
     x = torch.randn(rows, V, device="cuda", dtype=torch.bfloat16, requires_grad=True)
@@ -141,7 +160,7 @@ if __name__ == "__main__":
     torch.manual_seed(0)
     cases = {"attn": lambda: (attn(), attn(S=2048, B=4), attn(D=64, H=12, B=8, S=1024), attn(causal=False)),
              "attnvar": attn_variants,
-             "ln": layernorm, "adamw": adamw, "ce": cross_entropy, "gelu": bias_gelu}
+             "ln": layernorm, "adamw": adamw, "sgd": sgd, "ce": cross_entropy, "gelu": bias_gelu}
     for k, fn in cases.items():
         if a.only and k not in a.only.split(","):
             continue
