@@ -8,7 +8,10 @@ MI355X-first choices:
   * LayerNorm = wave-per-row HIP kernel (bf16 activations, fp32 statistics);
   * LM head tied to the token embedding, loss = fused softmax-CE with in-place backward;
   * vocab padded to a multiple of 128 (50257 -> 50304) so the head GEMM tiles cleanly;
-  * dropout omitted (0.0), as in throughput benchmarks of this class.
+  * dropout (``embd_pdrop`` / ``resid_pdrop``, default 0.0 as in throughput benchmarks of this class) keeps no
+    mask: a counter-based Philox mask per (key, element) is applied inside the fused residual-add + LayerNorm
+    kernel and regenerated in backward (``ops.dropout``); each rank's masks follow its own CUDA generator
+    (``torch.manual_seed``).  Dropout on the attention probabilities (``attn_pdrop``) is not implemented.
 """
 from __future__ import annotations
 
@@ -20,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import bias_gelu, cross_entropy, flash_attn_qkvpacked
+from ..ops import dropout as D
 from ..ops.embedding import Embedding
 from ..ops.fp8 import fp8_enabled, fp8_gelu_mlp, fp8_gelu_mlp_ok, fp8_recompute_safe
 from ..ops.linear import Linear, gelu_mlp, gelu_mlp_ok, linear, linear_bias_gelu, linear_bias_gelu_ok, linear_residual
@@ -39,6 +43,19 @@ class GPT2Config:
     # None = all of them when activation_checkpointing is on.  With 288 GB of HBM most of the recompute can be
     # bought back (bench.py --act-ckpt-layers auto sizes it to the memory)
     checkpoint_layers: int | None = None
+    # dropout on the embedding sum (wte + wpe) and on each residual branch (attention, MLP) -- GPT-2's published
+    # recipe is 0.1 for both.  attn_pdrop (the attention probabilities) would have to live inside the
+    # flash-attention kernels and is not implemented: any non-zero value raises.
+    embd_pdrop: float = 0.0
+    resid_pdrop: float = 0.0
+    attn_pdrop: float = 0.0
+
+    def __post_init__(self):
+        if self.attn_pdrop != 0:
+            raise ValueError("attn_pdrop != 0 is not supported: dropout on the attention probabilities needs a mask "
+                             "inside the flash-attention kernels, which keep no probability matrix to drop")
+        D.quantise(self.embd_pdrop)
+        D.quantise(self.resid_pdrop)
 
     @property
     def head_dim(self):
@@ -135,13 +152,24 @@ class GPT2Block(nn.Module):
         self.attn = CausalSelfAttention(cfg)
         self.ln_2 = LayerNorm(cfg.n_embd, eps=cfg.layer_norm_epsilon)
         self.mlp = MLP(cfg)
+        self.resid_pdrop = cfg.resid_pdrop
 
-    def forward(self, x, pending=None, pending_colsum=False):
+    def forward(self, x, pending=None, pending_colsum=False, key_1=None, key_2=None, pending_drop=None):
         """(x, pending) -> (x', mlp_out): the residual adds are fused into the following LayerNorm
         kernels (``pending`` is the previous block's branch output not yet added to the stream;
         ``pending_colsum``: it came from a biased Linear, whose bias gradient ln_1's backward sums).
         RESID_GEMM mode: (x, None) -> (x'', None), the branch outputs added to the stream by the projection GEMMs
-        and the norms reading the summed stream (``pending`` None: x already holds the previous block's MLP)."""
+        and the norms reading the summed stream (``pending`` None: x already holds the previous block's MLP).
+        Dropout (training with a non-zero rate): ``key_1`` / ``key_2`` are the int64[1] keys of this block's two
+        sites and ``pending_drop = (p, mode)`` says how ln_1 drops ``pending`` -- the previous MLP's output
+        ("residual") or, in block 0, the embedding sum ("sum"); ln_2 drops the attention branch plus its folded
+        bias.  The norm-side adds always run here: a GEMM cannot add the residual in front of the mask."""
+        if key_1 is not None:
+            h, x = self.ln_1.forward_add(x, pending, r_colsum=pending_colsum and FOLD_PROJ_BIAS,
+                                         dropout=(pending_drop[0], key_1, pending_drop[1]))
+            a, a_bias = self.attn(h, fold_bias=True) if FOLD_PROJ_BIAS else (self.attn(h), None)
+            y, x = self.ln_2.forward_add(x, a, a_bias, dropout=(self.resid_pdrop, key_2, "residual"))
+            return x, self.mlp(y)
         if pending is None:
             h, x = self.ln_1.forward_pass(x, r_colsum=pending_colsum)
         else:
@@ -211,6 +239,9 @@ class GPT2LMHeadModel(nn.Module):
         # embedding_dense_backward over B*S indices; now a slice copy of S rows)
         pending = self.wpe.weight[:S].unsqueeze(0).expand(B, S, -1)
         n_ckpt = self.config.checkpoint_layers if self.config.checkpoint_layers is not None else len(self.h)
+        cfg = self.config
+        if self.training and (cfg.embd_pdrop != 0 or cfg.resid_pdrop != 0):
+            return self._forward_dropout(x, pending, labels, n_ckpt)
         for i, blk in enumerate(self.h):
             # block i > 0 receives the previous MLP's c_proj output (biased Linear): ln_1 sums its gradient
             colsum = i > 0 and self._mlp_proj_bias[i - 1] and not fp8_enabled()
@@ -224,6 +255,28 @@ class GPT2LMHeadModel(nn.Module):
             x, _ = self.ln_f.forward_pass(x, r_colsum=last)
         else:
             x, _ = self.ln_f.forward_add(x, pending, r_colsum=last)
+        return self._head(x, labels)
+
+    def _forward_dropout(self, x, pending, labels, n_ckpt):
+        """The training forward with dropout: one ``draw_keys`` call for all 2 L + 1 sites (the embedding sum, and
+        per block the attention and the MLP branch); each block receives its two keys as tensor arguments, so a
+        checkpointed block's recompute sees the keys of its forward."""
+        cfg, L = self.config, len(self.h)
+        keys = D.draw_keys(2 * L + 1, x.device)
+        for i, blk in enumerate(self.h):
+            colsum = i > 0 and self._mlp_proj_bias[i - 1] and not fp8_enabled()
+            drop = (cfg.embd_pdrop, "sum") if i == 0 else (cfg.resid_pdrop, "residual")
+            args = (x, pending, colsum, keys[2 * i:2 * i + 1], keys[2 * i + 1:2 * i + 2], drop)
+            if cfg.activation_checkpointing and i < n_ckpt:
+                x, pending = torch.utils.checkpoint.checkpoint(fp8_recompute_safe(blk), *args, use_reentrant=False)
+            else:
+                x, pending = blk(*args)
+        last = self._mlp_proj_bias[-1] and not fp8_enabled() and FOLD_PROJ_BIAS
+        x, _ = self.ln_f.forward_add(x, pending, r_colsum=last,
+                                     dropout=(cfg.resid_pdrop, keys[2 * L:2 * L + 1], "residual"))
+        return self._head(x, labels)
+
+    def _head(self, x, labels):
         logits = linear(x, self.wte.weight)     # tied head (framework linear: transposed-layout dgrad)
         if labels is None:
             return logits

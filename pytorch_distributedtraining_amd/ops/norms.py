@@ -113,6 +113,83 @@ class _AddNormFn(torch.autograd.Function):
         return dx, dx, drb, dw, db, None, None, None
 
 
+DROP_MODES = ("residual", "sum")
+
+
+def drop_add_norm_ok(x, r, weight, r_bias=None) -> bool:
+    """The contract of the fused dropout + add + norm kernel (``pdt_dropout_add_norm_fwd``)."""
+    n = x.shape[-1]
+    return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and r.dtype == x.dtype
+            and weight.dtype in (torch.float32, torch.bfloat16) and (r_bias is None or r_bias.dtype == weight.dtype)
+            and n % 8 == 0 and n <= 2048)
+
+
+class _DropAddNormFn(torch.autograd.Function):
+    """(y, s) = (norm(s), s) with s = x + drop(r + rb) ("residual") or s = drop(x + r) ("sum") in one pass; the
+    mask is a function of (key, element index) (``ops.dropout``) and only the key is saved.  Backward in two steps:
+    the norm backward (with the stream's later gradient folded in) gives ds, then one masked pass turns it into dr
+    and sums dr per column for rb -- or, with ``r_colsum``, stashes that sum for the Linear that receives dr."""
+
+    @staticmethod
+    def forward(ctx, x, r, rb, weight, bias, key, eps, rms, r_colsum, thr, scale, mode):
+        shape = x.shape
+        n = shape[-1]
+        x2 = x.reshape(-1, n).contiguous()
+        r2 = r.reshape(-1, n).contiguous()
+        rows = x2.shape[0]
+        y = torch.empty_like(x2)
+        s = torch.empty_like(x2)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x2.device)
+        mean = None if rms else torch.empty(rows, dtype=torch.float32, device=x2.device)
+        _lib.call("pdt_dropout_add_norm_fwd", x2.data_ptr(), r2.data_ptr(), _lib.ptr(rb), s.data_ptr(),
+                  weight.data_ptr(), _lib.ptr(bias), y.data_ptr(), _lib.ptr(mean), rstd.data_ptr(), rows, n, float(eps),
+                  key.data_ptr(), thr, scale, DROP_MODES.index(mode), _lib.dtype_code(x2.dtype),
+                  _lib.dtype_code(weight.dtype), 1 if rms else 0, _lib.stream_handle(x2.device))
+        ctx.save_for_backward(s, weight, mean, rstd, key)
+        ctx.has_bias, ctx.rms, ctx.has_rb, ctx.r_colsum = bias is not None, rms, rb is not None, r_colsum
+        ctx.thr, ctx.scale, ctx.mode = thr, scale, mode
+        return y.view(shape), s.view(shape)
+
+    @staticmethod
+    def backward(ctx, dy, ds):
+        from .dropout import dropout_bwd
+        s, w, mean, rstd, key = ctx.saved_tensors
+        n = s.shape[-1]
+        shape = dy.shape if dy is not None else ds.shape
+        dy2 = dy.reshape(-1, n).contiguous() if dy is not None else torch.zeros_like(s)
+        ds2 = ds.reshape(-1, n).contiguous() if ds is not None else None
+        gs, dw, db, _ = _norm_bwd(dy2, s, w, mean, rstd, ctx.has_bias, ctx.rms, dres2=ds2)
+        need_rb = ctx.has_rb and ctx.needs_input_grad[2]
+        stash = ctx.r_colsum and not need_rb and ctx.needs_input_grad[1]
+        dr, drb = dropout_bwd(gs, key, ctx.thr, ctx.scale, w.dtype if (need_rb or stash) else None)
+        if stash:   # r came from a biased Linear in another FSDP unit: dr is that Linear's dY
+            stash_bias_grad(dr, drb)
+            drb = None
+        dr = dr.view(shape)
+        dx = dr if ctx.mode == "sum" else gs.view(shape)
+        return dx, dr, drb, dw, db, None, None, None, None, None, None, None
+
+
+def _drop_add_norm(x, r, weight, bias, eps, rms, r_bias, r_colsum, p, key, mode):
+    from .dropout import dropout, quantise
+    if mode not in DROP_MODES:
+        raise ValueError(f"dropout mode must be one of {DROP_MODES}, got {mode!r}")
+    if mode == "sum" and r_bias is not None:
+        raise ValueError("dropout mode 'sum' takes no r_bias")
+    thr, scale = quantise(p)
+    if drop_add_norm_ok(x, r, weight, r_bias) and x.shape == r.shape:
+        if key.dtype != torch.int64 or key.numel() != 1 or key.device != x.device:
+            raise ValueError("dropout key must be an int64[1] tensor on the input's device")
+        return _DropAddNormFn.apply(x, r, r_bias, weight, bias, key, eps, rms, bool(r_colsum), thr, scale, mode)
+    # outside the fused kernel's contract (CPU, other dtypes, N % 8 != 0, N > 2048): the standalone dropout -- the
+    # same mask, element for element -- composed with the existing add + norm
+    if mode == "sum":
+        s = dropout((x + r).contiguous(), p, key)
+        return norm_pass(s, weight, bias, eps, rms)
+    rd = dropout((r if r_bias is None else r + r_bias.to(r.dtype)).contiguous(), p, key)
+    return add_norm(x, rd, weight, bias, eps, rms)
+
+
 class _NormPassFn(torch.autograd.Function):
     """(y, x) = (norm(x), x): the residual stream passes through so that its LATER use's gradient ds comes back
     here and is folded into dx by the same backward pass (no separate add over the stream); ``r_colsum``: x came
@@ -251,11 +328,17 @@ def norm_pass(x, weight, bias=None, eps=1e-5, rms=False, r_colsum=False):
     return _NormPassFn.apply(x, weight, bias, eps, rms, bool(r_colsum))
 
 
-def add_norm(x, r, weight, bias=None, eps=1e-5, rms=False, r_bias=None, r_colsum=False):
+def add_norm(x, r, weight, bias=None, eps=1e-5, rms=False, r_bias=None, r_colsum=False, dropout=None):
     """Fused residual add + LayerNorm/RMSNorm: returns (norm(x + r + r_bias), x + r + r_bias); ``r_bias``
     (optional, [N], the norm's parameter dtype) is the bias of the Linear that produced r.  ``r_colsum``: r came
     from a biased Linear whose bias cannot be passed here (another FSDP unit's parameter): the backward still
-    sums its dx per column in the same pass and stashes it for that Linear (``ops.attention.take_bias_grad``)."""
+    sums its dx per column in the same pass and stashes it for that Linear (``ops.attention.take_bias_grad``).
+    ``dropout = (p, key, mode)`` (key: ``ops.dropout.draw_keys``) masks inside the same kernel: mode "residual"
+    returns (norm(s), s) with s = x + drop(r + r_bias), mode "sum" s = drop(x + r); None or p == 0 is the plain
+    path, unchanged."""
+    if dropout is not None and dropout[0] != 0:
+        p, key, mode = dropout
+        return _drop_add_norm(x, r, weight, bias, eps, rms, r_bias, r_colsum, p, key, mode)
     if (not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16) or r.dtype != x.dtype
             or (r_bias is not None and r_bias.dtype != weight.dtype)):
         s = x + r if r_bias is None else x + (r + r_bias.to(r.dtype))
@@ -308,9 +391,10 @@ class LayerNorm(nn.Module):
                 return layer_norm(x, self.weight, self.bias, self.eps)
         return layer_norm(x, self.weight, self.bias, self.eps)
 
-    def forward_add(self, x, r, r_bias=None, r_colsum=False):
-        """(LN(x + r + r_bias), x + r + r_bias) with one kernel pass (``add_norm``)."""
-        return _ln_forward_add(self, x, r, rms=False, r_bias=r_bias, r_colsum=r_colsum)
+    def forward_add(self, x, r, r_bias=None, r_colsum=False, dropout=None):
+        """(LN(x + r + r_bias), x + r + r_bias) with one kernel pass (``add_norm``); ``dropout = (p, key, mode)``
+        masks r (or the sum) in that pass."""
+        return _ln_forward_add(self, x, r, rms=False, r_bias=r_bias, r_colsum=r_colsum, dropout=dropout)
 
     def forward_pass(self, x, r_colsum=False):
         """(LN(x), x) for a stream the producing GEMM already summed (``norm_pass``)."""
@@ -320,13 +404,13 @@ class LayerNorm(nn.Module):
         return f"{self.normalized_shape}, eps={self.eps}"
 
 
-def _ln_forward_add(mod, x, r, rms, r_bias=None, r_colsum=False):
+def _ln_forward_add(mod, x, r, rms, r_bias=None, r_colsum=False, dropout=None):
     if x.is_cuda and torch.is_autocast_enabled("cuda"):
         dt = torch.get_autocast_dtype("cuda")
         with torch.autocast("cuda", enabled=False):
             return add_norm(x.to(dt), r.to(dt), mod.weight, getattr(mod, "bias", None), mod.eps, rms, r_bias,
-                            r_colsum)
-    return add_norm(x, r, mod.weight, getattr(mod, "bias", None), mod.eps, rms, r_bias, r_colsum)
+                            r_colsum, dropout)
+    return add_norm(x, r, mod.weight, getattr(mod, "bias", None), mod.eps, rms, r_bias, r_colsum, dropout)
 
 
 class RMSNorm(nn.Module):
@@ -342,8 +426,8 @@ class RMSNorm(nn.Module):
                 return rms_norm(x, self.weight, self.eps)
         return rms_norm(x, self.weight, self.eps)
 
-    def forward_add(self, x, r, r_bias=None, r_colsum=False):
-        return _ln_forward_add(self, x, r, rms=True, r_bias=r_bias, r_colsum=r_colsum)
+    def forward_add(self, x, r, r_bias=None, r_colsum=False, dropout=None):
+        return _ln_forward_add(self, x, r, rms=True, r_bias=r_bias, r_colsum=r_colsum, dropout=dropout)
 
     def forward_pass(self, x, r_colsum=False):
         """(RMSNorm(x), x) for a stream the producing GEMM already summed (``norm_pass``)."""

@@ -40,6 +40,7 @@ class RunConfig:
     optimizer: Dict[str, Any] = field(default_factory=lambda: {"lr": 1e-4, "betas": (0.9, 0.95), "eps": 1e-8,
                                                                 "weight_decay": 0.1})
     activation_checkpointing: bool = False
+    dropout: float = 0.0                    # GPT-2: embedding + residual dropout (embd_pdrop = resid_pdrop)
     bucket_cap_mb: float = 64.0
     first_bucket_mb: float = 8.0
     sync_batchnorm: bool = False

@@ -32,7 +32,10 @@ def build_model(cfg: RunConfig):
     if m.startswith("gpt2"):
         from .models import build_gpt2
         return build_gpt2(m, n_positions=max(1024, cfg.seq_len),
-                          activation_checkpointing=cfg.activation_checkpointing), "lm"
+                          activation_checkpointing=cfg.activation_checkpointing,
+                          embd_pdrop=cfg.dropout, resid_pdrop=cfg.dropout), "lm"
+    if cfg.dropout != 0:
+        raise ValueError(f"dropout is implemented for the gpt2 models only, not {m}")
     if m.startswith("llama"):
         from .models.llama import build_llama
         return build_llama(m, max_seq_len=max(cfg.seq_len, 2048),
@@ -204,11 +207,13 @@ def main(argv=None):
     ap.add_argument("--config", required=True)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None, dest="batch_size_per_device")
+    ap.add_argument("--dropout", type=float, default=None, help="GPT-2 embedding + residual dropout rate")
     ap.add_argument("--local-rank", "--local_rank", type=int, default=None, dest="local_rank")
     a = ap.parse_args(argv)
     if a.local_rank is not None:
         os.environ.setdefault("LOCAL_RANK", str(a.local_rank))
-    cfg = apply_env_overrides(load_config(a.config, steps=a.steps, batch_size_per_device=a.batch_size_per_device))
+    cfg = apply_env_overrides(load_config(a.config, steps=a.steps, batch_size_per_device=a.batch_size_per_device,
+                                          dropout=a.dropout))
     res = run(cfg)
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res, default=str), flush=True)
