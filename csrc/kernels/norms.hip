@@ -516,10 +516,12 @@ struct WinMap {
 };
 // 32-bit unsigned divisions (the host keeps rows < 2^31): the 64-bit division this was written with cost ~100 VALU
 // per call, once per row in every narrow-row norm pass of a Swin block
-__device__ __forceinline__ int64_t img_to_win(int64_t r, const WinMap& m) {
+// (smp: the sample index b = r / (H * W) the map computes anyway -- the scaled kernels index their per-sample scale by it)
+__device__ __forceinline__ int64_t img_to_win(int64_t r, const WinMap& m, uint32_t& smp) {
   const uint32_t per_img = (uint32_t)(m.H * m.W);
   const uint32_t r32 = (uint32_t)r;
   const uint32_t b = r32 / per_img;
+  smp = b;
   const uint32_t t = r32 - b * per_img;
   const uint32_t th = t / (uint32_t)m.W;
   int h = (int)th - m.shift, w = (int)(t - th * (uint32_t)m.W) - m.shift;
@@ -529,14 +531,22 @@ __device__ __forceinline__ int64_t img_to_win(int64_t r, const WinMap& m) {
   const uint32_t wh = (uint32_t)h / ws, i = (uint32_t)h - wh * ws, ww = (uint32_t)w / ws, j = (uint32_t)w - ww * ws;
   return (int64_t)b * per_img + (int64_t)((wh * ((uint32_t)m.W / ws) + ww) * ws * ws + i * ws + j);
 }
+__device__ __forceinline__ int64_t img_to_win(int64_t r, const WinMap& m) {
+  uint32_t smp;
+  return img_to_win(r, m, smp);
+}
 
-template <typename T, typename W, bool RMS>
+// SCALED (stochastic depth, drop_path.hip; mode bit 1 required, no rb): sample b = row / (H * W) adds its window-
+// order residual as s = x + sc[b] * r (fp32, one rounding) when sc[b] != 0 and otherwise does not load r at all --
+// s is then x's own bits, and inf / NaN in a dropped branch never enter the stream.
+template <typename T, typename W, bool RMS, bool SCALED = false>
 __global__ __launch_bounds__(NT) void norm_fwd_small(const T* __restrict__ x, const T* __restrict__ res,
                                                      const W* __restrict__ rb, T* __restrict__ sum_out,
                                                      const W* __restrict__ w,
                                                      const W* __restrict__ b, T* __restrict__ y,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                     int rows, int N, float eps, WinMap wm) {
+                                                     int rows, int N, float eps, WinMap wm,
+                                                     const float* __restrict__ sample_scale) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int sub = lane / SM_LPR, c0 = (lane % SM_LPR) * 4;
   const bool col_ok = c0 < N;
@@ -556,7 +566,18 @@ __global__ __launch_bounds__(NT) void norm_fwd_small(const T* __restrict__ x, co
     float v[4] = {0, 0, 0, 0};
     if (ok) {
       Vec4<T>::load(x + row * N + c0, v);
-      if (res != nullptr) {
+      if constexpr (SCALED) {
+        uint32_t smp;
+        const int64_t wrow = img_to_win(row, wm, smp);
+        const float sc = sample_scale[smp];
+        if (sc != 0.f) {
+          float r[4];
+          Vec4<T>::load(res + wrow * N + c0, r);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] = to_f<T>(from_f<T>(fmaf(sc, r[k], v[k])));
+        }
+        Vec4<T>::store(sum_out + row * N + c0, v);
+      } else if (res != nullptr) {
         float r[4];
         Vec4<T>::load(res + ((wm.mode & 2) ? img_to_win(row, wm) : row) * N + c0, r);
 #pragma unroll
@@ -587,13 +608,16 @@ __global__ __launch_bounds__(NT) void norm_fwd_small(const T* __restrict__ x, co
   }
 }
 
-template <typename T, typename W, bool RMS>
+// SCALED: dr_win = sc[b] * (the gradient of s), rounded once; a dropped sample's rows are written as exact zeros
+// (the buffer arrives uninitialised).  dx -- the gradient of the stream -- is the same either way.
+template <typename T, typename W, bool RMS, bool SCALED = false>
 __global__ __launch_bounds__(NT) void norm_bwd_small(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const W* __restrict__ w, const float* __restrict__ mean_in,
                                                      const float* __restrict__ rstd_in, const T* __restrict__ dres,
                                                      T* __restrict__ dx, float* __restrict__ dw_part,
                                                      float* __restrict__ db_part, float* __restrict__ ds_part,
-                                                     int rows, int N, WinMap wm, T* __restrict__ dr_win) {
+                                                     int rows, int N, WinMap wm, T* __restrict__ dr_win,
+                                                     const float* __restrict__ sample_scale) {
   __shared__ __attribute__((aligned(16))) float sred[3][RPB][64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int sub = lane / SM_LPR, c0 = (lane % SM_LPR) * 4;
@@ -635,7 +659,17 @@ __global__ __launch_bounds__(NT) void norm_bwd_small(const T* __restrict__ dy, c
 #pragma unroll
       for (int k = 0; k < 4; ++k) o[k] += rstd * (gw[k] - bs - xh[k] * a);
       Vec4<T>::store(dx + row * N + c0, o);
-      if (wm.mode & 2) Vec4<T>::store(dr_win + img_to_win(row, wm) * N + c0, o);   // the residual's gradient
+      if constexpr (SCALED) {
+        uint32_t smp;
+        const int64_t wrow = img_to_win(row, wm, smp);
+        const float sc = sample_scale[smp];
+        float d[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d[k] = sc != 0.f ? sc * o[k] : 0.f;
+        Vec4<T>::store(dr_win + wrow * N + c0, d);
+      } else {
+        if (wm.mode & 2) Vec4<T>::store(dr_win + img_to_win(row, wm) * N + c0, o);   // the residual's gradient
+      }
 #pragma unroll
       for (int k = 0; k < 4; ++k) dsa[k] += to_f<T>(from_f<T>(o[k]));
     }
@@ -669,13 +703,18 @@ using red::col_reduce;
 
 template <typename T, typename W, bool RMS>
 int launch_fwd(const void* x, const void* res, const void* rb, void* sum_out, const void* w, const void* b, void* y,
-               float* mean, float* rstd, int rows, int N, float eps, hipStream_t st, WinMap wm = {}) {
+               float* mean, float* rstd, int rows, int N, float eps, hipStream_t st, WinMap wm = {},
+               const float* sample_scale = nullptr) {
   const T* X = (const T*)x; const T* R = (const T*)res; T* S = (T*)sum_out; const W* RB = (const W*)rb;
   const W* Wt = (const W*)w; const W* B = (const W*)b; T* Y = (T*)y;
   if (wm.mode != 0 && !small_rows(N)) return (int)hipErrorInvalidValue;   // window maps: narrow rows only
-  if (small_rows(N)) {
+  if (sample_scale != nullptr) {   // stochastic depth: the window-order residual scaled or dropped per sample
+    if (!(wm.mode & 2) || R == nullptr || S == nullptr || RB != nullptr) return (int)hipErrorInvalidValue;
+    norm_fwd_small<T, W, RMS, true><<<grid_for(rows, SM_RPB, 256 * 16), NT, 0, st>>>(X, R, RB, S, Wt, B, Y, mean, rstd, rows,
+                                                                                    N, eps, wm, sample_scale);
+  } else if (small_rows(N)) {
     norm_fwd_small<T, W, RMS><<<grid_for(rows, SM_RPB, 256 * 16), NT, 0, st>>>(X, R, RB, S, Wt, B, Y, mean, rstd, rows, N,
-                                                                              eps, wm);
+                                                                              eps, wm, nullptr);
   } else if (N % 8 == 0 && N <= 8192) {
     // workgroups per CU: 64 (plain) / 96 (fused residual add) -- GPT-2 1.3B norms at 96 x 1024 tokens, 2,048
     // columns: plain 178 (16) -> 167.8 (32) -> 164.9 us (64), residual add 291 -> 250 us (96)
@@ -724,7 +763,7 @@ int bwd_partial_rows(int rows, int N) {
 template <typename T, typename W, bool RMS>
 int launch_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, const void* dres,
                void* dx, void* dw, void* db, void* ds, float* ws, int rows, int N, int accumulate, hipStream_t st,
-               WinMap wm = {}, void* dr_win = nullptr) {
+               WinMap wm = {}, void* dr_win = nullptr, const float* sample_scale = nullptr) {
   if (wm.mode != 0 && !small_rows(N)) return (int)hipErrorInvalidValue;
   if ((wm.mode & 2) && dr_win == nullptr) return (int)hipErrorInvalidValue;
   const T* DY = (const T*)dy; const T* X = (const T*)x; const W* Wt = (const W*)w; T* DX = (T*)dx;
@@ -734,9 +773,13 @@ int launch_bwd(const void* dy, const void* x, const void* w, const float* mean, 
   float* dbp = (db != nullptr) ? ws + (int64_t)R * N : nullptr;
   float* dsp = (ds != nullptr) ? ws + (int64_t)2 * R * N : nullptr;
   static const bool split_off = [] { const char* e = getenv("PDT_NORM_SPLIT"); return e && atoi(e) == 0; }();
-  if (small_rows(N)) {
+  if (sample_scale != nullptr) {
+    if (!(wm.mode & 2) || ds != nullptr) return (int)hipErrorInvalidValue;
+    norm_bwd_small<T, W, RMS, true><<<R, NT, 0, st>>>(DY, X, Wt, mean, rstd, DR, DX, dwp, dbp, dsp, rows, N, wm,
+                                                       (T*)dr_win, sample_scale);
+  } else if (small_rows(N)) {
     norm_bwd_small<T, W, RMS><<<R, NT, 0, st>>>(DY, X, Wt, mean, rstd, DR, DX, dwp, dbp, dsp, rows, N, wm,
-                                                 (T*)dr_win);
+                                                 (T*)dr_win, nullptr);
   } else if (split_rows_ok(N) && !split_off) {
     const int it = (N / RPB + 511) / 512;
 #define PDT_NS2(I, D, S) \
@@ -839,6 +882,44 @@ PDT_API int pdt_norm_bwd_win(const void* dy, const void* x, const void* w, const
   if (xdt == kBF16 && wdt == kBF16) return launch_bwd<bf16_t, bf16_t, R>(dy, x, w, mean, rstd, dres, dx, dw, db, nullptr, ws, rows, N, 0, st, wm, dr_win); \
   if (xdt == kBF16 && wdt == kF32) return launch_bwd<bf16_t, float, R>(dy, x, w, mean, rstd, dres, dx, dw, db, nullptr, ws, rows, N, 0, st, wm, dr_win);   \
   if (xdt == kF32 && wdt == kF32) return launch_bwd<float, float, R>(dy, x, w, mean, rstd, dres, dx, dw, db, nullptr, ws, rows, N, 0, st, wm, dr_win);
+  if (rms) { PDT_DISPATCH(true) } else { PDT_DISPATCH(false) }
+#undef PDT_DISPATCH
+  return (int)hipErrorInvalidValue;
+}
+
+// Stochastic depth at the window-mapped residual add (the block's attention branch): sample_scale [rows / (H * W)]
+// fp32 of 0 | scale (drop_path.hip).  mode bit 1 is required -- the residual is read from window order.  A kept
+// sample's s = x + sc * res, a dropped sample's s = x bit for bit (res is not read).
+PDT_API int pdt_norm_fwd_win_scaled(const void* x, const void* res, void* sum_out, const void* w, const void* b,
+                                    void* y, float* mean, float* rstd, int rows, int N, float eps, int xdt, int wdt,
+                                    int rms, int H, int W_, int ws, int shift, int mode,
+                                    const float* sample_scale, hipStream_t st) {
+  if (!small_rows(N) || ws <= 0 || H % ws || W_ % ws || shift < 0 || shift >= ws || rows % (H * W_) || !(mode & 2) ||
+      !res || !sum_out || !sample_scale)
+    return (int)hipErrorInvalidValue;
+  const WinMap wm{H, W_, ws, shift, mode};
+#define PDT_DISPATCH(R)                                                                                                 \
+  if (xdt == kBF16 && wdt == kBF16) return launch_fwd<bf16_t, bf16_t, R>(x, res, nullptr, sum_out, w, b, y, mean, rstd, rows, N, eps, st, wm, sample_scale); \
+  if (xdt == kBF16 && wdt == kF32) return launch_fwd<bf16_t, float, R>(x, res, nullptr, sum_out, w, b, y, mean, rstd, rows, N, eps, st, wm, sample_scale);   \
+  if (xdt == kF32 && wdt == kF32) return launch_fwd<float, float, R>(x, res, nullptr, sum_out, w, b, y, mean, rstd, rows, N, eps, st, wm, sample_scale);
+  if (rms) { PDT_DISPATCH(true) } else { PDT_DISPATCH(false) }
+#undef PDT_DISPATCH
+  return (int)hipErrorInvalidValue;
+}
+
+// ... and its backward: dr_win = sc * dx rounded once (exact zeros for a dropped sample); dx as pdt_norm_bwd_win.
+PDT_API int pdt_norm_bwd_win_scaled(const void* dy, const void* x, const void* w, const float* mean,
+                                    const float* rstd, const void* dres, void* dx, void* dw, void* db, float* ws,
+                                    int rows, int N, int xdt, int wdt, int rms, int H, int W_, int wsz, int shift,
+                                    int mode, void* dr_win, const float* sample_scale, hipStream_t st) {
+  if (!small_rows(N) || wsz <= 0 || H % wsz || W_ % wsz || shift < 0 || shift >= wsz || rows % (H * W_) ||
+      !(mode & 2) || !dr_win || !sample_scale)
+    return (int)hipErrorInvalidValue;
+  const WinMap wm{H, W_, wsz, shift, mode};
+#define PDT_DISPATCH(R)                                                                                                 \
+  if (xdt == kBF16 && wdt == kBF16) return launch_bwd<bf16_t, bf16_t, R>(dy, x, w, mean, rstd, dres, dx, dw, db, nullptr, ws, rows, N, 0, st, wm, dr_win, sample_scale); \
+  if (xdt == kBF16 && wdt == kF32) return launch_bwd<bf16_t, float, R>(dy, x, w, mean, rstd, dres, dx, dw, db, nullptr, ws, rows, N, 0, st, wm, dr_win, sample_scale);   \
+  if (xdt == kF32 && wdt == kF32) return launch_bwd<float, float, R>(dy, x, w, mean, rstd, dres, dx, dw, db, nullptr, ws, rows, N, 0, st, wm, dr_win, sample_scale);
   if (rms) { PDT_DISPATCH(true) } else { PDT_DISPATCH(false) }
 #undef PDT_DISPATCH
   return (int)hipErrorInvalidValue;

@@ -118,11 +118,19 @@ __device__ __forceinline__ void frag_cols(u16x8 (&f)[RB][KS], const bf16_t* __re
 }
 
 // ------------------------------------------------------------------------------------------------ forward
+// SCALED (stochastic depth, drop_path.hip): sc = sample_scale[token / rows_per_sample] is 0 or the site's scale.
+// rows_per_sample % 64 == 0 (host-checked), so a wave's 16-token tile lies in one sample and the branch on sc is
+// wave-uniform: a kept tile stores y = res + sc * (MLP(x) + b2), a dropped tile copies res to y bit for bit, issues
+// no MFMA and never loads x (inf / NaN in a dropped branch's input cannot reach y).  tiles_per_sample =
+// rows_per_sample / 16; the host keeps the tile count below 2^32 (one 32-bit division per tile).
+template <bool SCALED>
 __global__ __launch_bounds__(256) void swin_mlp_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w1,
                                                            const bf16_t* __restrict__ b1, const bf16_t* __restrict__ w2,
                                                            const bf16_t* __restrict__ b2,
                                                            const bf16_t* __restrict__ res, bf16_t* __restrict__ y,
-                                                           int64_t T, int C, int H) {
+                                                           int64_t T, int C, int H,
+                                                           const float* __restrict__ sample_scale,
+                                                           uint32_t tiles_per_sample) {
   __shared__ float b1s[HPAD], b2s[CPAD];
   const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
   for (int i = threadIdx.x; i < HPAD; i += 256) b1s[i] = i < H ? bf2f(b1[i]) : 0.f;
@@ -143,10 +151,41 @@ __global__ __launch_bounds__(256) void swin_mlp_fwd_kernel(const bf16_t* __restr
       xn[2 * ks + 1] = ld4(x, t, T, 32 * ks + 8 * g + 4, C, C);
     }
   };
-  if (tile < ntiles) load_x(tile);
+  // the scale of a tile's sample (wave-uniform: the tile index is)
+  auto tile_scale = [&](int64_t tl) {
+    return sample_scale[(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tl) / tiles_per_sample];
+  };
+  float sc = 1.f, sc_next = 1.f;
+  if constexpr (SCALED) {
+    if (tile < ntiles) {
+      sc_next = tile_scale(tile);
+      if (sc_next != 0.f) load_x(tile);
+    }
+  } else {
+    if (tile < ntiles) load_x(tile);
+  }
   for (; tile < ntiles; tile += stride) {
     const u16x8 B0 = pack2(xn[0], xn[1]), B1 = pack2(xn[2], xn[3]);
-    if (tile + stride < ntiles) load_x(tile + stride);     // next tile's x in flight during this one
+    if constexpr (SCALED) {
+      sc = sc_next;
+      if (tile + stride < ntiles) {
+        sc_next = tile_scale(tile + stride);
+        if (sc_next != 0.f) load_x(tile + stride);
+      }
+      if (sc == 0.f) {                                     // dropped sample: y = res, nothing else
+        const int64_t t = tile * 16 + r;
+        if (t < T) {
+#pragma unroll
+          for (int ob = 0; ob < 4; ++ob) {
+            const int o = 16 * ob + 4 * g;
+            if (o < C) *reinterpret_cast<uint2*>(y + t * C + o) = *reinterpret_cast<const uint2*>(res + t * C + o);
+          }
+        }
+        continue;
+      }
+    } else {
+      if (tile + stride < ntiles) load_x(tile + stride);     // next tile's x in flight during this one
+    }
     f32x4 acc1[8];
 #pragma unroll
     for (int hb = 0; hb < 8; ++hb) acc1[hb] = mfma16(A1[hb][1], B1, mfma16(A1[hb][0], B0, zero4()));
@@ -172,7 +211,13 @@ __global__ __launch_bounds__(256) void swin_mlp_fwd_kernel(const bf16_t* __restr
         const int o = 16 * ob + 4 * g;
         if (o < C) {
           f32x4 bb = *reinterpret_cast<const f32x4*>(b2s + o);
-          if (res) {                                      // fused residual add: y = res + MLP(x)
+          if constexpr (SCALED) {                         // y = res + sc * (MLP(x) + b2)
+            const uint2 rv = *reinterpret_cast<const uint2*>(res + t * C + o);
+            const float rf[4] = {bf2f((bf16_t)(rv.x & 0xffff)), bf2f((bf16_t)(rv.x >> 16)),
+                                 bf2f((bf16_t)(rv.y & 0xffff)), bf2f((bf16_t)(rv.y >> 16))};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { acc2[ob][i] = fmaf(sc, acc2[ob][i] + bb[i], rf[i]); bb[i] = 0.f; }
+          } else if (res) {                               // fused residual add: y = res + MLP(x)
             const uint2 rv = *reinterpret_cast<const uint2*>(res + t * C + o);
             bb[0] += bf2f((bf16_t)(rv.x & 0xffff)); bb[1] += bf2f((bf16_t)(rv.x >> 16));
             bb[2] += bf2f((bf16_t)(rv.y & 0xffff)); bb[3] += bf2f((bf16_t)(rv.y >> 16));
@@ -195,13 +240,40 @@ struct BwdLds {
   float b1s[HPAD];
 };
 
+// SCALED: sc = sample_scale[chunk / chunks_per_sample] (rows_per_sample % 64 == 0: a 64-token chunk lies in one
+// sample, so sc is the same in the whole workgroup).  A kept chunk runs on dy_eff = sc * dy (rounded to bf16); a
+// dropped chunk only gets zero dx rows, written in a pass of their own before the weights are loaded; the main loop
+// walks from kept chunk to kept chunk (next_kept), so it has no branch around its two barriers and a dropped chunk
+// costs no load, no recompute, no staging and no weight-gradient MFMA.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void swin_mlp_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
                                                            const bf16_t* __restrict__ w1, const bf16_t* __restrict__ b1,
                                                            const bf16_t* __restrict__ w2, bf16_t* __restrict__ dx,
-                                                           float* __restrict__ ws, int64_t T, int C, int H) {
+                                                           float* __restrict__ ws, int64_t T, int C, int H,
+                                                           const float* __restrict__ sample_scale,
+                                                           uint32_t chunks_per_sample) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   BwdLds& L = *reinterpret_cast<BwdLds*>(smem);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+  const int64_t nchunks = (T + 63) / 64;
+  const int tl = 16 * w + r;                        // this lane's token within the 64-token chunk
+  auto chunk_scale = [&](int64_t chunk) { return sample_scale[(uint32_t)chunk / chunks_per_sample]; };
+  // the first of this workgroup's chunks from c on that belongs to a kept sample
+  auto next_kept = [&](int64_t c) {
+    while (c < nchunks && chunk_scale(c) == 0.f) c += gridDim.x;
+    return c;
+  };
+  if constexpr (SCALED) {                           // dropped chunks are settled here: dx = 0, nothing else
+    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+      const int64_t t = c * 64 + tl;
+      if (chunk_scale(c) != 0.f || t >= T) continue;
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+        const int col = 16 * cb + 4 * g;
+        if (col < C) *reinterpret_cast<uint2*>(dx + t * C + col) = make_uint2(0u, 0u);
+      }
+    }
+  }
   for (int i = threadIdx.x; i < HPAD; i += 256) L.b1s[i] = i < H ? bf2f(b1[i]) : 0.f;
   u16x8 A1[8][2], Adh[8][2], Adx[4][4];
   frag_rows<8, 2>(A1, w1, H, C, r, g);              // a^T  = W1 x^T    rows hidden, K = channels
@@ -213,8 +285,6 @@ __global__ __launch_bounds__(256) void swin_mlp_bwd_kernel(const bf16_t* __restr
 #pragma unroll
     for (int b = 0; b < 4; ++b) { gw1[a][b] = zero4(); gw2[b][a] = zero4(); }
   __syncthreads();
-  const int64_t nchunks = (T + 63) / 64;
-  const int tl = 16 * w + r;                        // this lane's token within the 64-token chunk
   uint2 xn[4], dyn[4];                              // next chunk's x / dy rows, loaded one chunk ahead
   auto load_rows = [&](int64_t chunk) {
     const int64_t tt = chunk * 64 + tl;
@@ -225,12 +295,25 @@ __global__ __launch_bounds__(256) void swin_mlp_bwd_kernel(const bf16_t* __restr
       dyn[q] = ld4(dy, tt, T, c0, C, C);
     }
   };
-  if ((int64_t)blockIdx.x < nchunks) load_rows(blockIdx.x);
-  for (int64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+  int64_t ch = blockIdx.x;
+  if constexpr (SCALED) ch = next_kept(ch);
+  if (ch < nchunks) load_rows(ch);
+  while (ch < nchunks) {
     const int64_t t = ch * 64 + tl;
     const u16x8 Bx[2] = {pack2(xn[0], xn[1]), pack2(xn[2], xn[3])};
-    const u16x8 Bdy[2] = {pack2(dyn[0], dyn[1]), pack2(dyn[2], dyn[3])};
-    if (ch + gridDim.x < nchunks) load_rows(ch + gridDim.x);
+    u16x8 Bdy[2] = {pack2(dyn[0], dyn[1]), pack2(dyn[2], dyn[3])};
+    int64_t nx = 0;
+    if constexpr (SCALED) {
+      nx = next_kept(ch + gridDim.x);
+      if (nx < nchunks) load_rows(nx);
+      const float sc = chunk_scale(ch);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) Bdy[ks][j] = f2bf(sc * bf2f(Bdy[ks][j]));     // dy_eff = sc * dy
+    } else {
+      if (ch + gridDim.x < nchunks) load_rows(ch + gridDim.x);
+    }
     // stage [x | 1]^T and dy^T (feature-major) for the weight gradients
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -307,6 +390,8 @@ __global__ __launch_bounds__(256) void swin_mlp_bwd_kernel(const bf16_t* __restr
         }
     }
     __syncthreads();
+    if constexpr (SCALED) ch = nx;
+    else ch += gridDim.x;
   }
   // this workgroup's partial: ws[block][HPAD * CPAD (dW1 | db1 in col C)] then [CPAD * HPAD (dW2 | db2 in col H)]
   float* p1 = ws + (int64_t)blockIdx.x * (2 * HPAD * CPAD);
@@ -387,11 +472,38 @@ PDT_API int pdt_swin_mlp_fwd(const void* x, const void* w1, const void* b1, cons
   // workgroups (4 waves each; every wave loads the weights into VGPRs once): PDT_SWIN_MLP_FWD_WG overrides
   static const int cap = [] { const char* e = getenv("PDT_SWIN_MLP_FWD_WG"); return e ? atoi(e) : 1024; }();
   if (grid > cap) grid = cap;
-  swin_mlp_fwd_kernel<<<(int)grid, 256, 0, st>>>((const bf16_t*)x, (const bf16_t*)w1, (const bf16_t*)b1,
-                                                 (const bf16_t*)w2, (const bf16_t*)b2, (const bf16_t*)res, (bf16_t*)y,
-                                                 T, C, H);
+  swin_mlp_fwd_kernel<false><<<(int)grid, 256, 0, st>>>((const bf16_t*)x, (const bf16_t*)w1, (const bf16_t*)b1,
+                                                        (const bf16_t*)w2, (const bf16_t*)b2, (const bf16_t*)res,
+                                                        (bf16_t*)y, T, C, H, nullptr, 1u);
   return (int)hipGetLastError();
 }
+
+// Stochastic depth at the MLP branch: y = res + sc[b] * MLP(x) for kept samples, y = res for dropped ones
+// (sample_scale: T / rows_per_sample fp32 of 0 | scale, drop_path.hip).  res is required; rows_per_sample % 64 == 0
+// and T % rows_per_sample == 0 keep every 16-token tile and 64-token chunk inside one sample.
+static bool swin_mlp_scaled_ok(int64_t T, int64_t rows_per_sample, const void* sample_scale) {
+  return sample_scale != nullptr && rows_per_sample > 0 && rows_per_sample % 64 == 0 && T % rows_per_sample == 0 &&
+         T / 16 < ((int64_t)1 << 31) && rows_per_sample / 16 < ((int64_t)1 << 31);
+}
+
+PDT_API int pdt_swin_mlp_fwd_scaled(const void* x, const void* w1, const void* b1, const void* w2, const void* b2,
+                                    const void* res, void* y, int64_t T, int C, int H, const float* sample_scale,
+                                    int64_t rows_per_sample, hipStream_t st) {
+  if (T <= 0 || res == nullptr || !swin_mlp_shape_ok(C, H, x, y) || !swin_mlp_shape_ok(C, H, res, res) ||
+      !swin_mlp_scaled_ok(T, rows_per_sample, sample_scale))
+    return (int)hipErrorInvalidValue;
+  int64_t grid = (T / 16 + 3) / 4;
+  static const int cap = [] { const char* e = getenv("PDT_SWIN_MLP_FWD_WG"); return e ? atoi(e) : 1024; }();
+  if (grid > cap) grid = cap;
+  swin_mlp_fwd_kernel<true><<<(int)grid, 256, 0, st>>>((const bf16_t*)x, (const bf16_t*)w1, (const bf16_t*)b1,
+                                                       (const bf16_t*)w2, (const bf16_t*)b2, (const bf16_t*)res,
+                                                       (bf16_t*)y, T, C, H, sample_scale,
+                                                       (uint32_t)(rows_per_sample / 16));
+  return (int)hipGetLastError();
+}
+
+static int swin_mlp_wgrad_finish(void* dw1, void* db1, void* dw2, void* db2, int out_dt, float* ws, int nb, int C,
+                                 int H, hipStream_t st);
 
 // dx [T, C] bf16; weight / bias gradients written (not accumulated) in out_dt (kBF16 / kF32)
 PDT_API int pdt_swin_mlp_bwd(const void* x, const void* dy, const void* w1, const void* b1, const void* w2, void* dx,
@@ -401,13 +513,42 @@ PDT_API int pdt_swin_mlp_bwd(const void* x, const void* dy, const void* w1, cons
     return (int)hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute((const void*)swin_mlp_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)swin_mlp_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)sizeof(BwdLds)) != hipSuccess)
       return (int)hipErrorInvalidValue;
     attr = true;
   }
-  swin_mlp_bwd_kernel<<<nb, 256, sizeof(BwdLds), st>>>((const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)w1,
-                                                       (const bf16_t*)b1, (const bf16_t*)w2, (bf16_t*)dx, ws, T, C, H);
+  swin_mlp_bwd_kernel<false><<<nb, 256, sizeof(BwdLds), st>>>((const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)w1,
+                                                              (const bf16_t*)b1, (const bf16_t*)w2, (bf16_t*)dx, ws, T,
+                                                              C, H, nullptr, 1u);
+  return swin_mlp_wgrad_finish(dw1, db1, dw2, db2, out_dt, ws, nb, C, H, st);
+}
+
+// ... and its backward: dx = d(MLP)(sc * dy) for kept samples and 0 for dropped ones, which add nothing to the weight
+// gradients; the residual's gradient is dy itself (the caller's).  nb <= pdt_swin_mlp_bwd_blocks(T) as above.
+PDT_API int pdt_swin_mlp_bwd_scaled(const void* x, const void* dy, const void* w1, const void* b1, const void* w2,
+                                    void* dx, void* dw1, void* db1, void* dw2, void* db2, int out_dt, float* ws, int nb,
+                                    int64_t T, int C, int H, const float* sample_scale, int64_t rows_per_sample,
+                                    hipStream_t st) {
+  if (T <= 0 || nb <= 0 || !swin_mlp_shape_ok(C, H, x, dy) || !swin_mlp_shape_ok(C, H, dx, dx) ||
+      !swin_mlp_scaled_ok(T, rows_per_sample, sample_scale))
+    return (int)hipErrorInvalidValue;
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute((const void*)swin_mlp_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)sizeof(BwdLds)) != hipSuccess)
+      return (int)hipErrorInvalidValue;
+    attr = true;
+  }
+  swin_mlp_bwd_kernel<true><<<nb, 256, sizeof(BwdLds), st>>>(
+      (const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)w1, (const bf16_t*)b1, (const bf16_t*)w2, (bf16_t*)dx, ws, T,
+      C, H, sample_scale, (uint32_t)(rows_per_sample / 64));
+  return swin_mlp_wgrad_finish(dw1, db1, dw2, db2, out_dt, ws, nb, C, H, st);
+}
+
+// the two-stage sum of the nb workgroup partials into the weight / bias gradients
+static int swin_mlp_wgrad_finish(void* dw1, void* db1, void* dw2, void* db2, int out_dt, float* ws, int nb, int C,
+                                 int H, hipStream_t st) {
   const int slices = (nb + RED_SLICE - 1) / RED_SLICE;
   float* ws2 = ws + (int64_t)nb * 2 * HPAD * CPAD;
   swin_mlp_partial_sum<<<dim3(2 * HPAD * CPAD / 1024, slices), 256, 0, st>>>(ws, nb, ws2);

@@ -38,6 +38,8 @@ HIPCC_FLAGS = [
 PER_FILE_FLAGS = {
     # no-NaN float mode: fmaxf on MFMA outputs compiles to bare v_max3 (no canonicalising v_max x,x first)
     "flash_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans", "-mno-amdgpu-ieee"],
+    # x * scale and the residual add round separately, bit for bit what the torch composite computes
+    "drop_path.hip": ["-ffp-contract=off"],
 }
 
 

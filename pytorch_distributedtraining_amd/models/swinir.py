@@ -13,6 +13,13 @@ mask applied in-register, never materialised); the 3x3 convolutions on im2col + 
 (ops/conv.py; MIOpen has no bf16 implicit-GEMM solver for these channel counts); Linear weight gradients on
 the row-split batched GEMM (ops/linear.py); the MLP's bias + erf-GELU fused.  ``to_stock_torch`` swaps
 every one of them back to the stock torch module (the baseline of scripts/bench_torch_baseline.py).
+
+Stochastic depth (``drop_path_rate``, upstream's default for this model is 0.1; here 0.0 unless asked for): block k
+of the whole model drops each of its two residual branches per sample at rate ``linspace(0, rate, sum(depths))[k]``.
+One ``ops.dropout.draw_keys(2 * sum(depths))`` per training forward, key ``2k + j`` for branch j (0 attention,
+1 MLP), turned into per-sample scales by one kernel (ops/drop_path.py).  The attention branch is scaled or dropped
+inside the window-mapped add + LayerNorm, the MLP branch inside the fused MLP (a dropped sample's MLP is not
+computed); every other path composes ops.drop_path around today's op and trains identically.
 """
 from __future__ import annotations
 
@@ -24,10 +31,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops.activations import bias_gelu
+from ..ops import dropout as _dropout
 from ..ops.conv import Conv2d3x3, pixel_shuffle_affine
+from ..ops.drop_path import drop_path, drop_path_add, sample_scales, site_table
 from ..ops.linear import (Linear, _has_hooks, from_head_major_ok, linear, linear_from_head_major, linear_head_major,
                           linear_residual)
-from ..ops.swin_mlp import fused_mlp, fused_mlp_ok
+from ..ops.swin_mlp import fused_mlp, fused_mlp_ok, fused_mlp_scaled_ok
 from ..ops.norms import LayerNorm, add_layer_norm_from_windows, layer_norm_to_windows, window_norm_ok
 from ..ops.window_attention import (fused_window_ok, head_major_ok, window_attention, window_attention_table,
                                     window_partition_shifted, window_reverse_shifted_add)
@@ -136,8 +145,17 @@ class Mlp(nn.Module):
         self.fc2 = Linear(hidden, dim)
         self.native = True
 
-    def forward(self, x, residual=None):
-        """MLP(x), plus ``residual`` when given (fused into the kernel's epilogue on the fused path)."""
+    def forward(self, x, residual=None, sample_scale=None):
+        """MLP(x), plus ``residual`` when given (fused into the kernel's epilogue on the fused path).
+        ``sample_scale`` (fp32 [B] of 0 | scale): stochastic depth on the MLP branch -- inside the fused kernel where
+        its contract holds, otherwise ops.drop_path composed around today's op."""
+        if sample_scale is not None:
+            if x.is_cuda and self.native and fused_mlp_scaled_ok(x, residual, sample_scale) and fused_mlp_ok(
+                    x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias):
+                return fused_mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, residual,
+                                 sample_scale)
+            y = self.forward(x)
+            return drop_path(y, sample_scale) if residual is None else drop_path_add(residual, y, sample_scale)
         if x.is_cuda and self.native:
             if fused_mlp_ok(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias) and (
                     residual is None or (residual.dtype == torch.bfloat16 and residual.shape == x.shape)):
@@ -158,10 +176,12 @@ class Mlp(nn.Module):
 
 
 class SwinTransformerBlock(nn.Module):
-    def __init__(self, dim, input_resolution, num_heads, window_size=8, shift_size=0, mlp_ratio=2.0):
+    def __init__(self, dim, input_resolution, num_heads, window_size=8, shift_size=0, mlp_ratio=2.0, drop_path=0.0):
         super().__init__()
         self.dim, self.input_resolution, self.num_heads = dim, input_resolution, num_heads
         self.window_size, self.shift_size = window_size, shift_size
+        self.drop_path = float(drop_path)            # both residual branches, per sample (no parameters, no buffers)
+        self._drop_thr = _dropout.quantise(self.drop_path)[0]
         if min(input_resolution) <= window_size:
             self.shift_size, self.window_size = 0, min(input_resolution)
         self.norm1 = LayerNorm(dim)
@@ -195,9 +215,23 @@ class SwinTransformerBlock(nn.Module):
             m = cache[(H, W, device)] = self._mask((H, W)).to(device)
         return m
 
-    def forward(self, x, x_size):
+    def _own_scales(self, x):
+        """Called on its own (no scales from the model) in training mode at a non-zero rate: two fresh keys."""
+        cache = self.__dict__.setdefault("_drop_table_cache", {})
+        tab = cache.get(x.device)
+        if tab is None:
+            tab = cache[x.device] = site_table([self.drop_path] * 2, x.device)
+        sc = sample_scales(_dropout.draw_keys(2, x.device), tab, x.shape[0])
+        return sc[0], sc[1]
+
+    def forward(self, x, x_size, scales=None):
+        """``scales``: (attention, MLP) per-sample drop-path scales (fp32 [B] each, or None for no site) from the
+        model's one draw per forward."""
         H, W = x_size
         B, L, C = x.shape
+        if scales is None:
+            scales = self._own_scales(x) if self.training and self._drop_thr > 0 else (None, None)
+        sc_a, sc_m = scales
         if self.attn.native and fused_window_ok(x, H, W, self.window_size, self.shift_size) and (
                 x.dtype == torch.bfloat16 or not torch.is_autocast_enabled()):
             # roll + partition and reverse + roll + residual add as one permutation pass each (bf16, or fp32 --
@@ -213,14 +247,21 @@ class SwinTransformerBlock(nn.Module):
                 # (xs: x passed through norm1, so the residual's gradient is added inside norm1's backward pass)
                 win, xs = layer_norm_to_windows(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, H, W, ws, ss)
                 a = self.attn(win, mask=mask).to(x.dtype)
-                y, s = add_layer_norm_from_windows(xs, a, self.norm2.weight, self.norm2.bias, self.norm2.eps, H, W,
-                                                   ws, ss)
-                return self.mlp(y, residual=s)
+                if sc_a is None:
+                    y, s = add_layer_norm_from_windows(xs, a, self.norm2.weight, self.norm2.bias, self.norm2.eps, H, W,
+                                                       ws, ss)
+                else:
+                    y, s = add_layer_norm_from_windows(xs, a, self.norm2.weight, self.norm2.bias, self.norm2.eps, H, W,
+                                                       ws, ss, sample_scale=sc_a)
+                return self.mlp(y, residual=s) if sc_m is None else self.mlp(y, residual=s, sample_scale=sc_m)
             h = self.norm1(x).to(x.dtype)
             win = window_partition_shifted(h, H, W, ws, ss)
             a = self.attn(win, mask=mask).to(x.dtype)
+            if sc_a is not None:
+                a = drop_path(a, sc_a)       # window order: a sample's windows are contiguous, sample = row / (H * W)
             x = window_reverse_shifted_add(a, x, H, W, ws, ss)
-            return self.mlp(self.norm2(x), residual=x)
+            return self.mlp(self.norm2(x), residual=x) if sc_m is None else \
+                self.mlp(self.norm2(x), residual=x, sample_scale=sc_m)
         sc = x
         x = self.norm1(x).view(B, H, W, C)
         if self.shift_size > 0:
@@ -230,37 +271,43 @@ class SwinTransformerBlock(nn.Module):
         else:
             mask = None
         a = self.attn(window_partition(x, self.window_size), mask=mask)
+        if sc_a is not None:
+            a = drop_path(a, sc_a)
         x = window_reverse(a, self.window_size, H, W)
         if self.shift_size > 0:
             x = torch.roll(x, shifts=(self.shift_size, self.shift_size), dims=(1, 2))
         x = sc + x.reshape(B, L, C)
+        if sc_m is not None:
+            return drop_path_add(x, self.mlp(self.norm2(x)), sc_m)
         return x + self.mlp(self.norm2(x))
 
 
 class BasicLayer(nn.Module):
-    def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio):
+    def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio, drop_path=0.0):
         super().__init__()
+        dpr = list(drop_path) if isinstance(drop_path, (list, tuple)) else [drop_path] * depth
         self.blocks = nn.ModuleList([
             SwinTransformerBlock(dim, input_resolution, num_heads, window_size,
-                                 0 if i % 2 == 0 else window_size // 2, mlp_ratio) for i in range(depth)])
+                                 0 if i % 2 == 0 else window_size // 2, mlp_ratio, dpr[i]) for i in range(depth)])
 
-    def forward(self, x, x_size):
-        for b in self.blocks:
-            x = b(x, x_size)
+    def forward(self, x, x_size, scales=None):
+        """``scales``: one (attention, MLP) pair per block (SwinIR.forward_features), or None."""
+        for i, b in enumerate(self.blocks):
+            x = b(x, x_size) if scales is None else b(x, x_size, scales[i])
         return x
 
 
 class RSTB(nn.Module):
     """Residual Swin Transformer Block ('1conv' residual connection)."""
 
-    def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio):
+    def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio, drop_path=0.0):
         super().__init__()
-        self.residual_group = BasicLayer(dim, input_resolution, depth, num_heads, window_size, mlp_ratio)
+        self.residual_group = BasicLayer(dim, input_resolution, depth, num_heads, window_size, mlp_ratio, drop_path)
         self.conv = Conv2d3x3(dim, dim)
 
-    def forward(self, x, x_size):
+    def forward(self, x, x_size, scales=None):
         B, L, C = x.shape
-        y = self.residual_group(x, x_size)
+        y = self.residual_group(x, x_size) if scales is None else self.residual_group(x, x_size, scales)
         y = y.transpose(1, 2).reshape(B, C, *x_size)
         return self.conv(y).flatten(2).transpose(1, 2) + x
 
@@ -278,7 +325,7 @@ class PatchEmbed(nn.Module):
 class SwinIR(nn.Module):
     def __init__(self, img_size=64, in_chans=3, embed_dim=60, depths=(6, 6, 6, 6), num_heads=(6, 6, 6, 6),
                  window_size=8, mlp_ratio=2.0, upscale=2, img_range=1.0, upsampler="pixelshuffledirect",
-                 resi_connection="1conv", **_ignored):
+                 resi_connection="1conv", drop_path_rate=0.0, **_ignored):
         super().__init__()
         if upsampler != "pixelshuffledirect" or resi_connection != "1conv":
             raise NotImplementedError("this build implements the lightweight SwinIR-S path used by the reference "
@@ -289,8 +336,14 @@ class SwinIR(nn.Module):
         self.conv_first = Conv2d3x3(in_chans, embed_dim)
         self.patch_embed = PatchEmbed(embed_dim, norm=True)
         res = (img_size, img_size)
-        self.layers = nn.ModuleList([RSTB(embed_dim, res, d, h, window_size, mlp_ratio)
-                                     for d, h in zip(depths, num_heads)])
+        # stochastic depth, upstream's rule: linspace(0, rate, sum(depths)), block k uses dpr[k] at both branches
+        self.drop_path_rate = float(drop_path_rate)
+        self.depths = tuple(int(d) for d in depths)
+        dpr = [float(r) for r in torch.linspace(0, self.drop_path_rate, sum(self.depths))]
+        self.layers = nn.ModuleList([RSTB(embed_dim, res, d, h, window_size, mlp_ratio,
+                                          dpr[sum(self.depths[:i]):sum(self.depths[:i + 1])])
+                                     for i, (d, h) in enumerate(zip(depths, num_heads))])
+        self._drop_thr = [_dropout.quantise(r)[0] for r in dpr]      # per block; 0 = no site
         self.norm = LayerNorm(embed_dim)
         self.conv_after_body = Conv2d3x3(embed_dim, embed_dim)
         self.upsample = nn.Sequential(Conv2d3x3(embed_dim, upscale ** 2 * in_chans), nn.PixelShuffle(upscale))
@@ -312,11 +365,36 @@ class SwinIR(nn.Module):
         pw = (self.window_size - w % self.window_size) % self.window_size
         return F.pad(x, (0, pw, 0, ph), "reflect") if (ph or pw) else x
 
+    def drop_path_rates(self):
+        """The rate of each block, in model order."""
+        return [b.drop_path for layer in self.layers for b in layer.residual_group.blocks]
+
+    def _drop_path_scales(self, x):
+        """None (eval, or no site with a non-zero threshold), or per layer a list of (attention, MLP) per-sample
+        scale pairs: one draw_keys(2 * blocks) per forward, key 2k + j for branch j of block k; sites of
+        threshold 0 are no sites (None)."""
+        thr = self._drop_thr
+        if not self.training or not any(thr):
+            return None
+        rates = self.drop_path_rates()
+        cache = self.__dict__.setdefault("_drop_table_cache", {})
+        tab = cache.get(x.device)
+        if tab is None:     # the per-site thr / scale, on the device once
+            tab = cache[x.device] = site_table([r for r in rates for _ in (0, 1)], x.device)
+        sc = sample_scales(_dropout.draw_keys(2 * len(rates), x.device), tab, x.shape[0])
+        pairs = [(sc[2 * k], sc[2 * k + 1]) if thr[k] else (None, None) for k in range(len(rates))]
+        out, k = [], 0
+        for d in self.depths:
+            out.append(pairs[k:k + d])
+            k += d
+        return out
+
     def forward_features(self, x):
         x_size = (x.shape[2], x.shape[3])
         t = self.patch_embed(x)
-        for layer in self.layers:
-            t = layer(t, x_size)
+        scales = self._drop_path_scales(t)
+        for i, layer in enumerate(self.layers):
+            t = layer(t, x_size) if scales is None else layer(t, x_size, scales[i])
         t = self.norm(t)
         B, L, C = t.shape
         return t.transpose(1, 2).reshape(B, C, *x_size)

@@ -232,20 +232,26 @@ def window_norm_ok(x, H: int, W: int, ws: int, shift: int) -> bool:
             and C <= 64 and C % 4 == 0 and H % ws == 0 and W % ws == 0 and 0 <= shift < ws and _lib.available())
 
 
-def _win_norm_fwd(x2, res2, w, b, eps, geom, mode):
+def _win_norm_fwd(x2, res2, w, b, eps, geom, mode, sample_scale=None):
     rows, n = x2.shape
     H, W, ws, shift = geom
     y = torch.empty_like(x2)
     s = torch.empty_like(x2) if res2 is not None else None
     rstd = torch.empty(rows, dtype=torch.float32, device=x2.device)
     mean = torch.empty(rows, dtype=torch.float32, device=x2.device)
+    if sample_scale is not None:
+        _lib.call("pdt_norm_fwd_win_scaled", x2.data_ptr(), _lib.ptr(res2), _lib.ptr(s), w.data_ptr(), _lib.ptr(b),
+                  y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, n, float(eps), _lib.dtype_code(x2.dtype),
+                  _lib.dtype_code(w.dtype), 0, H, W, ws, shift, mode, sample_scale.data_ptr(),
+                  _lib.stream_handle(x2.device))
+        return y, s, mean, rstd
     _lib.call("pdt_norm_fwd_win", x2.data_ptr(), _lib.ptr(res2), _lib.ptr(s), w.data_ptr(), _lib.ptr(b), y.data_ptr(),
               mean.data_ptr(), rstd.data_ptr(), rows, n, float(eps), _lib.dtype_code(x2.dtype), _lib.dtype_code(w.dtype),
               0, H, W, ws, shift, mode, _lib.stream_handle(x2.device))
     return y, s, mean, rstd
 
 
-def _win_norm_bwd(dy2, x2, w, mean, rstd, need_b, dres2, geom, mode):
+def _win_norm_bwd(dy2, x2, w, mean, rstd, need_b, dres2, geom, mode, sample_scale=None):
     rows, n = x2.shape
     H, W, ws, shift = geom
     lib = _lib.require()
@@ -254,6 +260,12 @@ def _win_norm_bwd(dy2, x2, w, mean, rstd, need_b, dres2, geom, mode):
     dw = torch.empty_like(w)
     db = torch.empty_like(w) if need_b else None
     wsp = torch.empty(lib.pdt_norm_bwd_workspace_floats(rows, n), dtype=torch.float32, device=x2.device)
+    if sample_scale is not None:
+        _lib.call("pdt_norm_bwd_win_scaled", dy2.data_ptr(), x2.data_ptr(), w.data_ptr(), mean.data_ptr(),
+                  rstd.data_ptr(), _lib.ptr(dres2), dx.data_ptr(), dw.data_ptr(), _lib.ptr(db), wsp.data_ptr(), rows, n,
+                  _lib.dtype_code(x2.dtype), _lib.dtype_code(w.dtype), 0, H, W, ws, shift, mode, _lib.ptr(dr),
+                  sample_scale.data_ptr(), _lib.stream_handle(x2.device))
+        return dx, dr, dw, db
     _lib.call("pdt_norm_bwd_win", dy2.data_ptr(), x2.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
               _lib.ptr(dres2), dx.data_ptr(), dw.data_ptr(), _lib.ptr(db), wsp.data_ptr(), rows, n,
               _lib.dtype_code(x2.dtype), _lib.dtype_code(w.dtype), 0, H, W, ws, shift, mode, _lib.ptr(dr),
@@ -310,15 +322,46 @@ class _AddNormFromWindowsFn(torch.autograd.Function):
         return dx.view(ctx.shape), dr.view(ctx.wshape), dw, db, None, None
 
 
+class _ScaledAddNormFromWindowsFn(torch.autograd.Function):
+    """_AddNormFromWindowsFn with stochastic depth on the window-ordered branch: s = x + sc[b] * a_win for a kept
+    sample b, s = x bit for bit for a dropped one (its a_win rows are not read).  Backward: d(a_win) = sc[b] * d(s),
+    exact zeros for a dropped sample; d(x) = d(s) as without."""
+
+    @staticmethod
+    def forward(ctx, x, a_win, weight, bias, eps, geom, sample_scale):
+        B, L, C = x.shape
+        x2 = x.reshape(-1, C).contiguous()
+        a2 = a_win.reshape(-1, C).contiguous()
+        y, s, mean, rstd = _win_norm_fwd(x2, a2, weight, bias, eps, geom, 2, sample_scale)
+        ctx.save_for_backward(s, weight, mean, rstd, sample_scale)
+        ctx.geom, ctx.has_bias, ctx.shape, ctx.wshape = geom, bias is not None, x.shape, a_win.shape
+        return y.view(x.shape), s.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy, ds):
+        s, w, mean, rstd, sample_scale = ctx.saved_tensors
+        n = s.shape[-1]
+        dy2 = dy.reshape(-1, n).contiguous() if dy is not None else torch.zeros_like(s)
+        ds2 = ds.reshape(-1, n).contiguous() if ds is not None else None
+        dx, dr, dw, db = _win_norm_bwd(dy2, s, w, mean, rstd, ctx.has_bias, ds2, ctx.geom, 2, sample_scale)
+        return dx.view(ctx.shape), dr.view(ctx.wshape), dw, db, None, None, None
+
+
 def layer_norm_to_windows(x, weight, bias, eps, H, W, ws, shift):
     """(LayerNorm of [B, H*W, C] written in shifted-window order [B*nW, ws*ws, C], x) -- use the returned x for the
     residual so its gradient is folded into this norm's backward (see window_norm_ok)."""
     return _NormToWindowsFn.apply(x, weight, bias, eps, (H, W, ws, shift))
 
 
-def add_layer_norm_from_windows(x, a_win, weight, bias, eps, H, W, ws, shift):
-    """(LayerNorm(s), s), s = x + the window-ordered ``a_win`` put back in image order (see window_norm_ok)."""
-    return _AddNormFromWindowsFn.apply(x, a_win, weight, bias, eps, (H, W, ws, shift))
+def add_layer_norm_from_windows(x, a_win, weight, bias, eps, H, W, ws, shift, sample_scale=None):
+    """(LayerNorm(s), s), s = x + the window-ordered ``a_win`` put back in image order (see window_norm_ok).
+    ``sample_scale`` (fp32 ``[B]`` of 0 | scale, ops.drop_path.sample_scales): stochastic depth on ``a_win`` --
+    sample b adds ``sample_scale[b] * a_win``, or nothing where the scale is 0."""
+    if sample_scale is None:
+        return _AddNormFromWindowsFn.apply(x, a_win, weight, bias, eps, (H, W, ws, shift))
+    if sample_scale.dtype != torch.float32 or sample_scale.device != x.device or sample_scale.numel() != x.shape[0]:
+        raise ValueError("sample_scale must be an fp32 [B] tensor on x's device")
+    return _ScaledAddNormFromWindowsFn.apply(x, a_win, weight, bias, eps, (H, W, ws, shift), sample_scale.contiguous())
 
 
 def norm_pass(x, weight, bias=None, eps=1e-5, rms=False, r_colsum=False):

@@ -41,6 +41,7 @@ class RunConfig:
                                                                 "weight_decay": 0.1})
     activation_checkpointing: bool = False
     dropout: float = 0.0                    # GPT-2: embedding + residual dropout (embd_pdrop = resid_pdrop)
+    drop_path: float = 0.0                  # SwinIR: stochastic depth (drop_path_rate, ramped over the blocks)
     bucket_cap_mb: float = 64.0
     first_bucket_mb: float = 8.0
     sync_batchnorm: bool = False

@@ -29,6 +29,8 @@ from .run_config import RunConfig, apply_env_overrides, load_config, optimizer_n
 def build_model(cfg: RunConfig):
     """-> (model, kind) with kind in {"lm", "cls", "sr"}."""
     m = cfg.model
+    if cfg.drop_path != 0 and not m.startswith("swinir"):
+        raise ValueError(f"drop_path is implemented for the swinir models only, not {m}")
     if m.startswith("gpt2"):
         from .models import build_gpt2
         return build_gpt2(m, n_positions=max(1024, cfg.seq_len),
@@ -45,7 +47,7 @@ def build_model(cfg: RunConfig):
         return getattr(resnet, m)(num_classes=cfg.num_classes), "cls"
     if m.startswith("swinir"):
         from .models.swinir import swinir_s_x2
-        return swinir_s_x2(), "sr"
+        return swinir_s_x2(drop_path_rate=cfg.drop_path), "sr"
     if m == "srnet":
         from .models.srnet import Net
         return Net(upscale_factor=2), "sr"
@@ -208,12 +210,14 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None, dest="batch_size_per_device")
     ap.add_argument("--dropout", type=float, default=None, help="GPT-2 embedding + residual dropout rate")
+    ap.add_argument("--drop-path", type=float, default=None, dest="drop_path",
+                    help="SwinIR stochastic depth rate (drop_path_rate; upstream SwinIR defaults to 0.1)")
     ap.add_argument("--local-rank", "--local_rank", type=int, default=None, dest="local_rank")
     a = ap.parse_args(argv)
     if a.local_rank is not None:
         os.environ.setdefault("LOCAL_RANK", str(a.local_rank))
     cfg = apply_env_overrides(load_config(a.config, steps=a.steps, batch_size_per_device=a.batch_size_per_device,
-                                          dropout=a.dropout))
+                                          dropout=a.dropout, drop_path=a.drop_path))
     res = run(cfg)
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res, default=str), flush=True)
