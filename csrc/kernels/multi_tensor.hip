@@ -11,6 +11,9 @@
 // and a block table (int32 pairs: tensor index, chunk index).  The engines keep parameters in flat
 // buffers, so the common case is a 1-entry table whose chunks tile the whole shard; the table form
 // is what lets a user hand the optimizer arbitrary parameter lists and still get ONE launch.
+// The parameter-EMA variants of the step kernels take a second table with the same row order, ONE pointer
+// per row (the fp32 average; null = the row keeps none): the 6-word row is full for AdamW and is shared
+// with every other kernel here, so it is not widened.
 //
 // Sync-free step: the grad multiplier (1/loss_scale * clip coefficient) and the found_inf flag live in
 // device memory, produced by pdt_l2norm_* + pdt_clip_coef, so no host round trip sits between
@@ -44,11 +47,17 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
   p -= h.step_size * m / denom;
 }
 
+// Parameter EMA (torch.optim.swa_utils.get_ema_multi_avg_fn: lerp(ema, p, 1 - decay)): e <- e + w * (p - e) with the
+// freshly updated fp32 p still in registers.  The product and the sum may contract into one FMA (one rounding fewer).
+__device__ __forceinline__ float ema_elem(float e, float p, float w) { return e + w * (p - e); }
+
 // One block processes one chunk of one tensor; 4 elements per thread per iteration (16-B loads).
-template <typename G>
+// EMA: ``ema_tab[row]`` is the row's fp32 average (null = none), updated from the new p next to the P / M / V / O stores.
+template <typename G, bool EMA = false>
 __global__ __launch_bounds__(MT_THREADS) void adamw_mt_kernel(
     const int64_t* __restrict__ meta, const int* __restrict__ blk, int chunk, AdamHyper h,
-    const float* __restrict__ gscale, const int* __restrict__ found_inf, const float* __restrict__ dstep) {
+    const float* __restrict__ gscale, const int* __restrict__ found_inf, const float* __restrict__ dstep,
+    const int64_t* __restrict__ ema_tab = nullptr, float ema_w = 0.f) {
   if (found_inf != nullptr && *found_inf != 0) return;  // GradScaler semantics: skip the step
   const float gs = gscale ? *gscale : 1.f;
   if (dstep != nullptr) {   // graph-capturable: the step count lives on the device, bias corrections here
@@ -63,10 +72,12 @@ __global__ __launch_bounds__(MT_THREADS) void adamw_mt_kernel(
   float* __restrict__ M = reinterpret_cast<float*>(mt[2]);
   float* __restrict__ V = reinterpret_cast<float*>(mt[3]);
   bf16_t* __restrict__ O = reinterpret_cast<bf16_t*>(mt[4]);
+  const int64_t ea = EMA ? ema_tab[t] : 0;
+  float* __restrict__ E = reinterpret_cast<float*>(ea);
   const int64_t n = mt[5];
   const int64_t beg = (int64_t)c * chunk;
   const int64_t end = beg + chunk < n ? beg + chunk : n;
-  const bool vec_ok = ((mt[0] | mt[1] | mt[2] | mt[3]) & 15) == 0 && (mt[4] & 7) == 0 &&
+  const bool vec_ok = ((mt[0] | mt[1] | mt[2] | mt[3] | ea) & 15) == 0 && (mt[4] & 7) == 0 &&
                       (sizeof(G) == 4 || (mt[1] & 7) == 0);
   int64_t i = beg + (int64_t)threadIdx.x * 4;
   if (vec_ok) {
@@ -93,6 +104,12 @@ __global__ __launch_bounds__(MT_THREADS) void adamw_mt_kernel(
       *reinterpret_cast<f32x4*>(P + i) = p;
       *reinterpret_cast<f32x4*>(M + i) = m;
       *reinterpret_cast<f32x4*>(V + i) = v;
+      if (EMA && E) {
+        f32x4 e = *reinterpret_cast<f32x4*>(E + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e[k] = ema_elem(e[k], p[k], ema_w);
+        *reinterpret_cast<f32x4*>(E + i) = e;
+      }
       if (O) {
         u16x4 o;
 #pragma unroll
@@ -105,6 +122,7 @@ __global__ __launch_bounds__(MT_THREADS) void adamw_mt_kernel(
       float p = P[i], m = M[i], v = V[i];
       adam_elem<G>(p, m, v, to_f<G>(Gr[i]) * gs, h);
       P[i] = p; M[i] = m; V[i] = v;
+      if (EMA && E) E[i] = ema_elem(E[i], p, ema_w);
       if (O) O[i] = f2bf(p);
     }
   } else {
@@ -112,6 +130,7 @@ __global__ __launch_bounds__(MT_THREADS) void adamw_mt_kernel(
       float p = P[j], m = M[j], v = V[j];
       adam_elem<G>(p, m, v, to_f<G>(Gr[j]) * gs, h);
       P[j] = p; M[j] = m; V[j] = v;
+      if (EMA && E) E[j] = ema_elem(E[j], p, ema_w);
       if (O) O[j] = f2bf(p);
     }
   }
@@ -135,10 +154,11 @@ __device__ __forceinline__ void sgd_elem(float& p, float& b, float g, const SgdH
 }
 
 // Same table / block form as adamw_mt_kernel: [param f32, grad, momentum_buffer f32 or null, unused, bf16 out or
-// null, numel].  A null buffer column (momentum == 0) is neither read nor written.
-template <typename G, bool MOM>
+// null, numel].  A null buffer column (momentum == 0) is neither read nor written.  E: the row's fp32 parameter
+// average (EMA instantiations only; null = none).
+template <typename G, bool MOM, bool EMA>
 __device__ __forceinline__ void sgd_chunk(const int64_t* __restrict__ mt, int c, int chunk, const SgdHyper& h,
-                                          float gs) {
+                                          float gs, float* __restrict__ E, float ema_w) {
   float* __restrict__ P = reinterpret_cast<float*>(mt[0]);
   const G* __restrict__ Gr = reinterpret_cast<const G*>(mt[1]);
   float* __restrict__ M = reinterpret_cast<float*>(mt[2]);
@@ -146,8 +166,8 @@ __device__ __forceinline__ void sgd_chunk(const int64_t* __restrict__ mt, int c,
   const int64_t n = mt[5];
   const int64_t beg = (int64_t)c * chunk;
   const int64_t end = beg + chunk < n ? beg + chunk : n;
-  const bool vec_ok = ((mt[0] | mt[1] | mt[2]) & 15) == 0 && (mt[4] & 7) == 0 &&
-                      (sizeof(G) == 4 || (mt[1] & 7) == 0);
+  const bool vec_ok = ((mt[0] | mt[1] | mt[2] | (EMA ? reinterpret_cast<int64_t>(E) : 0)) & 15) == 0 &&
+                      (mt[4] & 7) == 0 && (sizeof(G) == 4 || (mt[1] & 7) == 0);
   int64_t i = beg + (int64_t)threadIdx.x * 4;
   if (vec_ok) {
     for (; i + 3 < end; i += MT_THREADS * 4) {
@@ -172,6 +192,12 @@ __device__ __forceinline__ void sgd_chunk(const int64_t* __restrict__ mt, int c,
       }
       *reinterpret_cast<f32x4*>(P + i) = p;
       if (MOM) *reinterpret_cast<f32x4*>(M + i) = m;
+      if (EMA && E) {
+        f32x4 e = *reinterpret_cast<f32x4*>(E + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e[k] = ema_elem(e[k], p[k], ema_w);
+        *reinterpret_cast<f32x4*>(E + i) = e;
+      }
       if (O) {
         u16x4 o;
 #pragma unroll
@@ -185,6 +211,7 @@ __device__ __forceinline__ void sgd_chunk(const int64_t* __restrict__ mt, int c,
       sgd_elem<MOM>(p, m, to_f<G>(Gr[i]) * gs, h);
       P[i] = p;
       if (MOM) M[i] = m;
+      if (EMA && E) E[i] = ema_elem(E[i], p, ema_w);
       if (O) O[i] = f2bf(p);
     }
   } else {
@@ -193,6 +220,7 @@ __device__ __forceinline__ void sgd_chunk(const int64_t* __restrict__ mt, int c,
       sgd_elem<MOM>(p, m, to_f<G>(Gr[j]) * gs, h);
       P[j] = p;
       if (MOM) M[j] = m;
+      if (EMA && E) E[j] = ema_elem(E[j], p, ema_w);
       if (O) O[j] = f2bf(p);
     }
   }
@@ -200,19 +228,21 @@ __device__ __forceinline__ void sgd_chunk(const int64_t* __restrict__ mt, int c,
 
 // Fused SGD (momentum / Nesterov, L2 weight decay).  lr_ptr: the learning rate read from the device, so a
 // captured step follows a schedule that fills the tensor in place.
-template <typename G>
+template <typename G, bool EMA = false>
 __global__ __launch_bounds__(MT_THREADS) void sgd_mt_kernel(
     const int64_t* __restrict__ meta, const int* __restrict__ blk, int chunk, SgdHyper h,
-    const float* __restrict__ gscale, const int* __restrict__ found_inf, const float* __restrict__ lr_ptr) {
+    const float* __restrict__ gscale, const int* __restrict__ found_inf, const float* __restrict__ lr_ptr,
+    const int64_t* __restrict__ ema_tab = nullptr, float ema_w = 0.f) {
   if (found_inf != nullptr && *found_inf != 0) return;  // GradScaler semantics: skip the step
   const float gs = gscale ? *gscale : 1.f;
   if (lr_ptr != nullptr) h.lr = *lr_ptr;
   const int t = blk[2 * blockIdx.x], c = blk[2 * blockIdx.x + 1];
   const int64_t* mt = meta + (int64_t)t * MT_META;
+  float* E = EMA ? reinterpret_cast<float*>(ema_tab[t]) : nullptr;
   if (h.momentum != 0.f && mt[2] != 0)
-    sgd_chunk<G, true>(mt, c, chunk, h, gs);
+    sgd_chunk<G, true, EMA>(mt, c, chunk, h, gs, E, ema_w);
   else
-    sgd_chunk<G, false>(mt, c, chunk, h, gs);
+    sgd_chunk<G, false, EMA>(mt, c, chunk, h, gs, E, ema_w);
 }
 
 // Sum of squares per block (ptr0 of each tensor), written to partial[blockIdx.x].
@@ -332,6 +362,48 @@ __global__ __launch_bounds__(MT_THREADS) void add_mt_kernel(const int64_t* __res
   for (int64_t j = beg + threadIdx.x; j < end; j += MT_THREADS) D[j] = from_f<T>(to_f<T>(D[j]) + to_f<T>(S[j]));
 }
 
+// a <-> b over a tensor list (ptr0 = a fp32, ptr1 = b fp32, ptr2 = bf16 copy of the NEW a or null) in one pass:
+// puts the averaged weights (b = the EMA state) into the masters and refreshes the bf16 compute copy with the
+// optimizer epilogue's rounding; the same launch again undoes it exactly.
+__global__ __launch_bounds__(MT_THREADS) void swap_mt_kernel(const int64_t* __restrict__ meta,
+                                                             const int* __restrict__ blk, int chunk) {
+  const int t = blk[2 * blockIdx.x], c = blk[2 * blockIdx.x + 1];
+  const int64_t* mt = meta + (int64_t)t * MT_META;
+  float* __restrict__ A = reinterpret_cast<float*>(mt[0]);
+  float* __restrict__ B = reinterpret_cast<float*>(mt[1]);
+  bf16_t* __restrict__ O = reinterpret_cast<bf16_t*>(mt[2]);
+  const int64_t n = mt[5];
+  const int64_t beg = (int64_t)c * chunk;
+  const int64_t end = beg + chunk < n ? beg + chunk : n;
+  const bool vec_ok = ((mt[0] | mt[1]) & 15) == 0 && (mt[2] & 7) == 0;
+  if (vec_ok) {
+    int64_t i = beg + (int64_t)threadIdx.x * 4;
+    for (; i + 3 < end; i += MT_THREADS * 4) {
+      const f32x4 a = *reinterpret_cast<f32x4*>(A + i);
+      const f32x4 b = *reinterpret_cast<f32x4*>(B + i);
+      *reinterpret_cast<f32x4*>(A + i) = b;
+      *reinterpret_cast<f32x4*>(B + i) = a;
+      if (O) {
+        u16x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = f2bf(b[k]);
+        *reinterpret_cast<u16x4*>(O + i) = o;
+      }
+    }
+    for (; i < end; ++i) {   // tail (fewer than 4 left for this thread)
+      const float a = A[i], b = B[i];
+      A[i] = b; B[i] = a;
+      if (O) O[i] = f2bf(b);
+    }
+  } else {
+    for (int64_t j = beg + threadIdx.x; j < end; j += MT_THREADS) {
+      const float a = A[j], b = B[j];
+      A[j] = b; B[j] = a;
+      if (O) O[j] = f2bf(b);
+    }
+  }
+}
+
 // Device step counter of a param group: +1 unless the (all-reduced) found_inf flag says the step is skipped
 // (torch.amp.GradScaler skips optimizer.step() on overflow, so Adam's bias-correction step must not move).
 __global__ void step_inc_kernel(float* __restrict__ dstep, const int* __restrict__ found_inf) {
@@ -358,6 +430,25 @@ PDT_API int pdt_adamw_mt(const int64_t* meta, const int* blk, int nblocks, int c
   return (int)hipGetLastError();
 }
 
+// pdt_adamw_mt + parameter EMA: ema_tab[row] = the row's fp32 average or null, ema_w = 1 - decay
+PDT_API int pdt_adamw_ema_mt(const int64_t* meta, const int* blk, int nblocks, int chunk, int grad_dtype, float lr,
+                             float beta1, float beta2, float eps, float wd, float step_size, float bc2_sqrt,
+                             int decoupled, const float* gscale, const int* found_inf, const float* dstep,
+                             const int64_t* ema_tab, float ema_w, hipStream_t stream) {
+  AdamHyper h{lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, decoupled};
+  if (nblocks <= 0) return 0;
+  if (ema_tab == nullptr) return (int)hipErrorInvalidValue;
+  if (grad_dtype == kF32)
+    adamw_mt_kernel<float, true><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, dstep,
+                                                                     ema_tab, ema_w);
+  else if (grad_dtype == kBF16)
+    adamw_mt_kernel<bf16_t, true><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, dstep,
+                                                                      ema_tab, ema_w);
+  else
+    return (int)hipErrorInvalidValue;
+  return (int)hipGetLastError();
+}
+
 // lr_ptr (device, nullable) overrides lr; a non-zero momentum needs the buffer column of every row set
 PDT_API int pdt_sgd_mt(const int64_t* meta, const int* blk, int nblocks, int chunk, int grad_dtype, float lr,
                        float momentum, float wd, int nesterov, const float* gscale, const int* found_inf,
@@ -370,6 +461,31 @@ PDT_API int pdt_sgd_mt(const int64_t* meta, const int* blk, int nblocks, int chu
     sgd_mt_kernel<bf16_t><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, lr_ptr);
   else
     return (int)hipErrorInvalidValue;
+  return (int)hipGetLastError();
+}
+
+// pdt_sgd_mt + parameter EMA (as pdt_adamw_ema_mt)
+PDT_API int pdt_sgd_ema_mt(const int64_t* meta, const int* blk, int nblocks, int chunk, int grad_dtype, float lr,
+                           float momentum, float wd, int nesterov, const float* gscale, const int* found_inf,
+                           const float* lr_ptr, const int64_t* ema_tab, float ema_w, hipStream_t stream) {
+  SgdHyper h{lr, momentum, wd, nesterov};
+  if (nblocks <= 0) return 0;
+  if (ema_tab == nullptr) return (int)hipErrorInvalidValue;
+  if (grad_dtype == kF32)
+    sgd_mt_kernel<float, true><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, lr_ptr,
+                                                                   ema_tab, ema_w);
+  else if (grad_dtype == kBF16)
+    sgd_mt_kernel<bf16_t, true><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, lr_ptr,
+                                                                    ema_tab, ema_w);
+  else
+    return (int)hipErrorInvalidValue;
+  return (int)hipGetLastError();
+}
+
+// rows [a fp32, b fp32, bf16 out or null, -, -, numel]: a <-> b, out = bf16(new a)
+PDT_API int pdt_swap_mt(const int64_t* meta, const int* blk, int nblocks, int chunk, hipStream_t stream) {
+  if (nblocks <= 0) return 0;
+  swap_mt_kernel<<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk);
   return (int)hipGetLastError();
 }
 

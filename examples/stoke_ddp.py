@@ -17,6 +17,7 @@ MI355X (--fp16 amp selects fp16 + loss scaling with the AMPConfig above).  Data:
 patches unless --inputDir/--targetDir point at image folders (no network access here).
 """
 import argparse
+import contextlib
 import os
 import sys
 
@@ -52,6 +53,9 @@ def parse():
     p.add_argument("--samples", type=int, default=512, help="synthetic dataset size")
     p.add_argument("--lr-size", type=int, default=64, help="synthetic LR patch size (reference: 128)")
     p.add_argument("--fp16", default="bf16", choices=["bf16", "amp", "none"])
+    p.add_argument("--ema_decay", "--ema-decay", type=float, default=0.0,
+                   help="keep an exponential moving average of the weights with this decay (e.g. 0.999) and validate "
+                        "it; 0 = off")
     p.add_argument("--cpu", action="store_true")
     p.add_argument("--ckpt-dir", default="checkpoint/")
     p.add_argument("--metrics", default="runs/stoke_ddp_metrics.jsonl")
@@ -88,7 +92,8 @@ def train(loader, t: Trainer, sched1, epoch, sink):
 def validate(loader, t: Trainer, epoch, sink):
     t.model_access.eval()
     vals = torch.zeros(4, dtype=torch.float64)
-    with torch.no_grad():
+    # --ema_decay: the averaged weights are swapped in for the pass and out again after it
+    with (t.averaged_parameters() if t.param_ema_decay is not None else contextlib.nullcontext()), torch.no_grad():
         for inputs, targets in loader:
             outputs = t.model(inputs).float()
             vals += torch.tensor([float(t.loss(outputs, targets)), metrics.mae(outputs, targets),
@@ -125,7 +130,8 @@ def main():
                 gpu=gpu, fp16=None if opt.fp16 == "none" else opt.fp16, distributed=dist_opt,
                 fairscale_oss=world > 1, fairscale_sddp=world > 1, grad_accum_steps=2,
                 configs=[amp_config, ddp_config, oss_config],
-                grad_clip=ClipGradNormConfig(max_norm=opt.grad_clip, norm_type=2.0))
+                grad_clip=ClipGradNormConfig(max_norm=opt.grad_clip, norm_type=2.0),
+                param_ema_decay=opt.ema_decay or None)
 
     if opt.inputDir and opt.targetDir and os.path.isdir(opt.inputDir):
         full = PairedImageDataset(opt.inputDir, opt.targetDir)

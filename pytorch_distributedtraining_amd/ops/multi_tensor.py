@@ -89,11 +89,45 @@ class TensorTable:
         return self._key
 
 
+class PointerTable:
+    """One device pointer per row (null where the row has none), in the row order of the ``TensorTable`` it goes with:
+    the second table of the parameter-EMA step kernels (the 6-word row has no free column under AdamW)."""
+
+    def __init__(self, tensors: Sequence[torch.Tensor | None], like: Sequence[torch.Tensor]):
+        assert len(tensors) == len(like)
+        dev = like[0].device if len(like) else torch.device("cpu")
+        host = torch.zeros(max(len(tensors), 1), dtype=torch.int64, pin_memory=dev.type == "cuda")
+        for i, (t, ref) in enumerate(zip(tensors, like)):
+            if t is not None:
+                assert t.dtype == torch.float32 and t.device == ref.device and t.numel() == ref.numel()
+                assert _dense(t) and (t.dim() <= 1 or all(
+                    a == b for a, b, k in zip(t.stride(), ref.stride(), ref.shape) if k != 1)), \
+                    "the parameter average must share its parameter's memory layout"
+                host[i] = t.data_ptr()
+        if dev.type == "cuda":
+            self.ptrs = host.to(dev, non_blocking=True)
+            self._host = host                                 # pinned source stays alive with the table
+        else:
+            self.ptrs = host
+        self._key = TensorTable.make_key([tensors])
+
+    def key(self) -> tuple:
+        return self._key
+
+
 class TableCache:
     """Rebuilds a TensorTable only when the pointer set changes."""
 
     def __init__(self):
         self._tables = {}
+
+    def get_pointers(self, name, tensors, like) -> PointerTable:
+        key = TensorTable.make_key([tensors])
+        t = self._tables.get(name)
+        if t is None or t.key() != key:
+            t = PointerTable(tensors, like)
+            self._tables[name] = t
+        return t
 
     def get(self, name, cols, chunk=DEFAULT_CHUNK) -> TensorTable:
         key = TensorTable.make_key(cols)
@@ -196,10 +230,30 @@ def scale_(tensors: Sequence[torch.Tensor], s: torch.Tensor) -> None:
                   _lib.dtype_code(dt), s.data_ptr(), _lib.stream_handle(dev))
 
 
+def _ema_weight(emas, ema_decay, who: str, rows: int):
+    """-> ``w = 1 - decay`` (computed in double, rounded to fp32 where it is used), or None when the average is off."""
+    if emas is None and ema_decay is None:
+        return None
+    if emas is None or ema_decay is None:
+        raise ValueError(f"{who}: emas and ema_decay go together")
+    d = float(ema_decay)
+    if not 0.0 < d < 1.0:
+        raise ValueError(f"{who}: ema_decay must be in (0, 1), got {ema_decay}")
+    if len(emas) != rows:
+        raise ValueError(f"{who}: {len(emas)} averages for {rows} parameters (None where a parameter keeps none)")
+    return 1.0 - d
+
+
+def _ema_cpu_(e: torch.Tensor, p: torch.Tensor, w: float) -> None:
+    """ema <- ema + w * (p - ema) in fp32 (the kernels' formula; torch's lerp for w < 0.5)."""
+    e.add_(p - e, alpha=float(torch.tensor(w, dtype=torch.float32)))
+
+
 def adamw_step(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta2: float, eps: float,
                weight_decay: float, step: int, decoupled: bool = True, grad_scale: torch.Tensor | None = None,
                found_inf: torch.Tensor | None = None, out_bf16=None, table: TensorTable | None = None,
-               dstep: torch.Tensor | None = None) -> None:
+               dstep: torch.Tensor | None = None, emas=None, ema_decay: float | None = None,
+               ema_table: PointerTable | None = None) -> None:
     """One fused (multi-tensor) AdamW update.  fp32 params/state; grads fp32 or bf16.
 
     grad_scale: optional device scalar multiplied into every gradient (unscale x clip coefficient).
@@ -207,7 +261,11 @@ def adamw_step(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float,
     out_bf16: optional list of bf16 tensors receiving the updated params (low-precision compute copy /
     all-gather input for the sharded engines).
     dstep: optional device fp32 step count (already incremented): the kernel derives the bias corrections
-    from it, so the launch replays correctly inside a captured HIP graph (``step`` is then ignored)."""
+    from it, so the launch replays correctly inside a captured HIP graph (``step`` is then ignored).
+    emas / ema_decay: optional fp32 parameter averages (one per parameter, None where a parameter keeps none) updated
+    in the same launch from the new fp32 parameter: ``ema += (1 - ema_decay) * (p - ema)``; a skipped step leaves
+    them alone.  ``ema_table``: the cached ``PointerTable`` of ``emas`` that goes with ``table``."""
+    ema_w = _ema_weight(emas, ema_decay, "adamw_step", len(params))
     if dstep is not None and params and params[0].device.type != "cuda":
         step = int(dstep.item())
     bc1 = 1.0 - beta1 ** step
@@ -234,6 +292,8 @@ def adamw_step(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float,
             v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
             denom = v.sqrt() / bc2_sqrt + eps
             p.addcdiv_(m, denom, value=-step_size)
+            if ema_w is not None and emas[i] is not None:
+                _ema_cpu_(emas[i], p, ema_w)
             if out_bf16 is not None and out_bf16[i] is not None:
                 out_bf16[i].copy_(p)
         return
@@ -242,6 +302,14 @@ def adamw_step(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float,
         cols = [list(params), list(grads), list(exp_avgs), list(exp_avg_sqs)]
         cols.append(list(out_bf16) if out_bf16 is not None else [None] * len(params))
         table = _cache.get(("adamw", gdt, len(params), id(params[0])), cols)
+    if ema_w is not None:
+        if ema_table is None:
+            ema_table = _cache.get_pointers(("adamw-ema", gdt, len(params), id(params[0])), list(emas), list(params))
+        _lib.call("pdt_adamw_ema_mt", table.meta.data_ptr(), table.blk.data_ptr(), table.nblocks, table.chunk,
+                  _lib.dtype_code(gdt), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                  float(step_size), float(bc2_sqrt), 1 if decoupled else 0, _lib.ptr(grad_scale),
+                  _lib.ptr(found_inf), _lib.ptr(dstep), ema_table.ptrs.data_ptr(), ema_w, _lib.stream_handle(dev))
+        return
     _lib.call("pdt_adamw_mt", table.meta.data_ptr(), table.blk.data_ptr(), table.nblocks, table.chunk,
               _lib.dtype_code(gdt), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
               float(step_size), float(bc2_sqrt), 1 if decoupled else 0, _lib.ptr(grad_scale), _lib.ptr(found_inf),
@@ -250,14 +318,16 @@ def adamw_step(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float,
 
 def sgd_step(params, grads, bufs, *, lr, momentum: float, weight_decay: float, nesterov: bool,
              grad_scale: torch.Tensor | None = None, found_inf: torch.Tensor | None = None, out_bf16=None,
-             table: TensorTable | None = None) -> None:
+             table: TensorTable | None = None, emas=None, ema_decay: float | None = None,
+             ema_table: PointerTable | None = None) -> None:
     """One fused (multi-tensor) SGD update, torch.optim.SGD's math with dampening 0 (torch/optim/sgd.py
     ``_single_tensor_sgd``).  fp32 params / momentum buffers; grads fp32 or bf16.
 
     lr: a float, or a 1-element fp32 tensor on the parameters' device -- the kernel then reads the rate from the
     device, so a launch captured into a HIP graph follows a schedule that ``fill_``s the tensor.
     bufs: the momentum buffers (zeros before the first step); ignored, and may be None, when ``momentum`` is 0.
-    grad_scale / found_inf / out_bf16 / table: as in ``adamw_step``."""
+    grad_scale / found_inf / out_bf16 / table / emas / ema_decay / ema_table: as in ``adamw_step``."""
+    ema_w = _ema_weight(emas, ema_decay, "sgd_step", len(params))
     if len(params) == 0:
         return
     dev = params[0].device
@@ -284,6 +354,8 @@ def sgd_step(params, grads, bufs, *, lr, momentum: float, weight_decay: float, n
                 p.sub_(g * rate)
             else:
                 p.add_(g, alpha=-rate)
+            if ema_w is not None and emas[i] is not None:
+                _ema_cpu_(emas[i], p, ema_w)
             if out_bf16 is not None and out_bf16[i] is not None:
                 out_bf16[i].copy_(p)
         return
@@ -301,9 +373,48 @@ def sgd_step(params, grads, bufs, *, lr, momentum: float, weight_decay: float, n
         cols = [list(params), list(grads), list(bufs) if use_mom else none, none,
                 list(out_bf16) if out_bf16 is not None else none]
         table = _cache.get(("sgd", gdt, len(params), id(params[0])), cols)
+    if ema_w is not None:
+        if ema_table is None:
+            ema_table = _cache.get_pointers(("sgd-ema", gdt, len(params), id(params[0])), list(emas), list(params))
+        _lib.call("pdt_sgd_ema_mt", table.meta.data_ptr(), table.blk.data_ptr(), table.nblocks, table.chunk,
+                  _lib.dtype_code(gdt), lr_val, float(momentum), float(weight_decay), 1 if nesterov else 0,
+                  _lib.ptr(grad_scale), _lib.ptr(found_inf), lr_ptr, ema_table.ptrs.data_ptr(), ema_w,
+                  _lib.stream_handle(dev))
+        return
     _lib.call("pdt_sgd_mt", table.meta.data_ptr(), table.blk.data_ptr(), table.nblocks, table.chunk,
               _lib.dtype_code(gdt), lr_val, float(momentum), float(weight_decay), 1 if nesterov else 0,
               _lib.ptr(grad_scale), _lib.ptr(found_inf), lr_ptr, _lib.stream_handle(dev))
+
+
+def swap_(a_list: Sequence[torch.Tensor], b_list: Sequence[torch.Tensor], out_bf16=None,
+          table: TensorTable | None = None) -> None:
+    """Exchange two lists of fp32 tensors element by element (``a <-> b``) in ONE launch on CUDA; ``out_bf16[i]``
+    (bf16, or None) receives the new ``a`` with the optimizer epilogue's rounding.  A second call undoes the first
+    exactly.  Puts parameter averages (``b``) into the fp32 masters (``a``) and refreshes the compute copy."""
+    a_list, b_list = list(a_list), list(b_list)
+    if len(a_list) != len(b_list):
+        raise ValueError("swap_: the two lists differ in length")
+    if not a_list:
+        return
+    outs = list(out_bf16) if out_bf16 is not None else [None] * len(a_list)
+    for a, b, o in zip(a_list, b_list, outs):
+        if a.dtype != torch.float32 or b.dtype != torch.float32 or a.numel() != b.numel() or a.device != b.device:
+            raise TypeError("swap_: pairs of fp32 tensors of equal size on one device")
+        if o is not None and (o.dtype != torch.bfloat16 or o.numel() != a.numel() or o.device != a.device):
+            raise TypeError("swap_: out_bf16 entries are bf16 tensors of the pair's size and device")
+    dev = a_list[0].device
+    if dev.type != "cuda":
+        for a, b, o in zip(a_list, b_list, outs):
+            t = a.clone()
+            a.copy_(b)
+            b.copy_(t)
+            if o is not None:
+                o.copy_(a)
+        return
+    if table is None:
+        table = _cache.get(("swap", len(a_list), id(a_list[0])), [a_list, b_list, outs])
+    _lib.call("pdt_swap_mt", table.meta.data_ptr(), table.blk.data_ptr(), table.nblocks, table.chunk,
+              _lib.stream_handle(dev))
 
 
 def step_inc_(dstep: torch.Tensor, found_inf: torch.Tensor | None = None) -> None:

@@ -9,7 +9,16 @@ A FusedOptimizer
   kernels, so no host round trip sits between backward and the update, and a set ``found_inf`` changes nothing;
 * writes the bf16 compute copy ``_pdt_lp_shard`` of a parameter in the kernel's epilogue (a non-bf16 copy is
   refreshed by a plain copy) and records it in ``_pdt_lp_version``;
-* honours a ``capturable`` param-group flag: every quantity that changes from step to step is read on the device.
+* honours a ``capturable`` param-group flag: every quantity that changes from step to step is read on the device;
+* keeps, with the param-group key ``ema_decay`` set (default None = off, no state key, the launches of before), an
+  exponential moving average of each fp32 master in ``state[p]["ema"]``, updated by the step kernel from the new
+  parameter it holds in registers: ``ema += (1 - ema_decay) * (p_new - ema)``, i.e.
+  ``torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(d))`` updated once before the first step
+  and once after every step.  Being optimizer state it is sharded, consolidated, checkpointed and reloaded by every
+  engine like the moments; a skipped (``found_inf``) step leaves it alone.  Unlike the reference, a parameter that
+  gets no gradient in a step does not advance its average in that step, and buffers are not averaged.  The key is
+  read on the host at each step (fixed at capture time under graph capture, like AdamW's ``lr``).
+  ``swap_ema_()`` exchanges parameters and averages in place (validation with the averaged weights) and back.
 """
 from __future__ import annotations
 
@@ -41,8 +50,68 @@ class FusedOptimizer(Optimizer):
     _label = "FusedOptimizer"     # the public name error messages use
 
     def __init__(self, params, defaults):
+        self._check_ema_decay(defaults.get("ema_decay"))
         super().__init__(params, defaults)
+        for group in self.param_groups:
+            self._check_ema_decay(group.get("ema_decay"))
         self._tables = mt.TableCache()
+        self.ema_swapped = False      # True while swap_ema_() has the averaged weights in the parameters
+
+    # ------------------------------------------------------------------ parameter EMA
+    @classmethod
+    def _check_ema_decay(cls, d):
+        if d is not None and not (isinstance(d, (int, float)) and 0.0 < float(d) < 1.0):
+            raise ValueError(f"{cls._label}: ema_decay must be None (off) or a float in (0, 1), got {d!r}")
+
+    def _check_not_swapped(self):
+        if self.ema_swapped:
+            raise RuntimeError(f"{self._label}.step(): the averaged weights are swapped in (swap_ema_); swap them "
+                               "out before the next step")
+
+    def _emas(self, group, ps):
+        """-> (the fp32 averages of ``ps``, decay) for a group with ``ema_decay`` set, else (None, None).  The state
+        is created here, at a parameter's first step with the average on: a clone of the fp32 master before that
+        step's update, in its memory layout."""
+        d = group.get("ema_decay")
+        if d is None:
+            return None, None
+        self._check_ema_decay(d)
+        emas = []
+        for p in ps:
+            st = self.state[p]
+            e = st.get("ema")
+            if e is None:
+                e = st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
+                p._pdt_opt_state = True
+            emas.append(e)
+        return emas, float(d)
+
+    @torch.no_grad()
+    def swap_ema_(self) -> int:
+        """Exchange every parameter that has an ``"ema"`` state with its average, in place: ONE ``swap_`` launch per
+        (group, device), which also writes the bf16 compute copies (``_pdt_lp_shard``); other copies are refreshed by
+        a plain copy.  The same call swaps back, bit for bit.  Call it at a step boundary; ``step()`` raises while
+        ``ema_swapped`` is set.  Returns the number of parameters exchanged (0 before the first step: the average of
+        a parameter that has not stepped is the parameter)."""
+        n = 0
+        for gi, group in enumerate(self.param_groups):
+            by_dev = {}
+            for p in group["params"]:
+                if p in self.state and self.state[p].get("ema") is not None:
+                    by_dev.setdefault(p.device, []).append(p)
+            for dev, ps in by_dev.items():
+                emas = [self.state[p]["ema"] for p in ps]
+                lps, lp_other = self._compute_copies(ps)
+                outs = lps if any(x is not None for x in lps) else None
+                table = None
+                if dev.type == "cuda":
+                    table = self._tables.get(("swap", gi, dev), [ps, emas, outs if outs is not None else
+                                                                  [None] * len(ps)])
+                mt.swap_(ps, emas, outs, table=table)
+                self._refresh_copies(ps, lp_other)
+                n += len(ps)
+        self.ema_swapped = not self.ema_swapped
+        return n
 
     def _present(self, group):
         """The group's parameters that have a gradient this step (fp32 masters with dense gradients only)."""
@@ -133,6 +202,15 @@ class FusedOptimizer(Optimizer):
             torch._foreach_zero_(grads)
 
     def load_state_dict(self, state_dict):
+        if self.ema_swapped:
+            raise RuntimeError(f"{self._label}.load_state_dict(): swap the averaged weights out first (swap_ema_)")
+        decays = [g.get("ema_decay") for g in self.param_groups]
         super().load_state_dict(state_dict)
+        for g, d in zip(self.param_groups, decays):
+            # torch replaces the group's keys by the checkpoint's: one written without the average (no key, or
+            # off) must not switch off the average this optimizer was built with -- it starts at the next step
+            if g.get("ema_decay") is None and d is not None:
+                g["ema_decay"] = d
+            self._check_ema_decay(g.get("ema_decay"))
         for p in self.state:
             p._pdt_opt_state = True   # engines must not re-lay-out this parameter any more (DDP rebuild)

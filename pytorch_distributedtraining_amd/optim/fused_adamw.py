@@ -13,6 +13,8 @@
   captured kernel increments, and the AdamW kernel derives its bias corrections from it, so a training step
   captured into a HIP graph (``utils.graphs.GraphedStep``) replays with the right step every time.  The
   learning rate is read when the step is captured (a schedule needs a re-capture).
+* Parameter EMA (``ema_decay``, a param-group key, default None = off): ``state[p]["ema"]``, updated by the same
+  launch -- see ``FusedOptimizer``.  The state layout is torch's plus that key, which torch.optim.AdamW carries.
 * Sharded engines: a parameter carrying ``_pdt_lp_shard`` (FSDP / ZeRO flat shards) gets its bf16
   compute copy written by the same kernel (fused cast epilogue = the all-gather input).
 
@@ -32,12 +34,12 @@ class FusedAdamW(FusedOptimizer):
     _label = "FusedAdamW"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
-                 decoupled=True, capturable=False, **_ignored):
+                 decoupled=True, capturable=False, ema_decay=None, **_ignored):
         if amsgrad:
             raise ValueError("FusedAdamW: amsgrad is not supported")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                         maximize=False, foreach=None, capturable=capturable, differentiable=False, fused=None,
-                        decoupled=decoupled)
+                        decoupled=decoupled, ema_decay=ema_decay)
         super().__init__(params, defaults)
         self._dsteps: dict = {}
 
@@ -103,6 +105,7 @@ class FusedAdamW(FusedOptimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._check_not_swapped()
         for gi, group in enumerate(self.param_groups):
             beta1, beta2 = group["betas"]
             lr = float(group["lr"]) if not torch.is_tensor(group["lr"]) else float(group["lr"].item())
@@ -142,16 +145,21 @@ class FusedAdamW(FusedOptimizer):
                 vs = [self.state[p]["exp_avg_sq"] for p in ps]
                 lps, lp_other = self._compute_copies(ps)
                 has_lp = any(x is not None for x in lps)
-                table = None
+                emas, ema_decay = self._emas(group, ps)
+                table = ema_table = None
                 if dev.type == "cuda":
                     cols = [ps, grads, ms, vs, lps if has_lp else [None] * len(ps)]
                     name = (gi, gdt, ckey if dstep is not None else 0)
                     used.add(name)
                     table = self._tables.get(name, cols)
+                    if emas is not None:      # the averages' pointers: a second table under a name of its own
+                        used.add(name + ("ema",))
+                        ema_table = self._tables.get_pointers(name + ("ema",), emas, ps)
                 mt.adamw_step(ps, grads, ms, vs, lr=lr, beta1=beta1, beta2=beta2, eps=group["eps"],
                               weight_decay=group["weight_decay"], step=max(step, 1),
                               decoupled=group.get("decoupled", True), grad_scale=grad_scale, found_inf=found_inf,
-                              out_bf16=lps if has_lp else None, table=table, dstep=dstep)
+                              out_bf16=lps if has_lp else None, table=table, dstep=dstep, emas=emas,
+                              ema_decay=ema_decay, ema_table=ema_table)
                 self._refresh_copies(ps, lp_other)
             if buckets:
                 # tables of this group's counters that no longer exist (a split counter, a reloaded checkpoint)

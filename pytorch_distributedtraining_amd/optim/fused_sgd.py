@@ -10,7 +10,8 @@ multi-tensor launch per (param group, grad dtype, device).
 * Learning-rate schedules under graph capture: a ``group["lr"]`` that is a tensor on the parameters' device is read
   by the kernel from the device (no ``.item()``), so a captured step follows a scheduler that ``fill_``s it in place
   (torch/optim/lr_scheduler.py ``_update_param_group_val``).  A float is passed by value, i.e. read at capture.
-* Sync-free mixed precision, sharded engines' bf16 compute copies: as ``FusedOptimizer`` describes.
+* Sync-free mixed precision, sharded engines' bf16 compute copies, the parameter EMA (``ema_decay``, a param-group
+  key beyond torch's, default None = off; ``state[p]["ema"]``): as ``FusedOptimizer`` describes.
 
 Stated limits (each raises): ``dampening != 0``, ``maximize=True``, Nesterov without momentum (torch's own rule)
 are ValueErrors; sparse gradients a RuntimeError; non-fp32 parameters a TypeError.
@@ -28,7 +29,7 @@ class FusedSGD(FusedOptimizer):
     _label = "FusedSGD"
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
-                 capturable=False, **_ignored):
+                 capturable=False, ema_decay=None, **_ignored):
         if dampening != 0:
             raise ValueError("FusedSGD: dampening is not supported")
         if maximize:
@@ -39,6 +40,8 @@ class FusedSGD(FusedOptimizer):
             raise ValueError(f"FusedSGD: invalid momentum {momentum} / weight_decay {weight_decay}")
         defaults = dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=nesterov,
                         maximize=False, foreach=None, differentiable=False, fused=None)
+        if ema_decay is not None:      # the one key beyond torch's, stored only when set: off, the groups are torch's
+            defaults["ema_decay"] = ema_decay
         # ``capturable`` is accepted for symmetry with FusedAdamW and not stored (the group keys stay torch's):
         # SGD keeps no step count, so every step is capturable as it is
         super().__init__(params, defaults)
@@ -56,6 +59,7 @@ class FusedSGD(FusedOptimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._check_not_swapped()
         for gi, group in enumerate(self.param_groups):
             if group.get("dampening", 0) != 0 or group.get("maximize", False):
                 raise ValueError("FusedSGD: dampening / maximize are not supported")
@@ -75,13 +79,17 @@ class FusedSGD(FusedOptimizer):
                 bufs = [self._buffer(p) for p in ps] if momentum != 0 else None
                 lps, lp_other = self._compute_copies(ps)
                 has_lp = any(x is not None for x in lps)
-                table = None
+                emas, ema_decay = self._emas(group, ps)
+                table = ema_table = None
                 if dev.type == "cuda":
                     none = [None] * len(ps)
                     table = self._tables.get((gi, gdt, dev), [ps, grads, bufs if bufs is not None else none, none,
                                                               lps if has_lp else none])
+                    if emas is not None:      # the averages' pointers: a second table under a name of its own
+                        ema_table = self._tables.get_pointers((gi, gdt, dev, "ema"), emas, ps)
                 mt.sgd_step(ps, grads, bufs, lr=lr, momentum=momentum, weight_decay=group["weight_decay"],
                             nesterov=nesterov, grad_scale=grad_scale, found_inf=found_inf,
-                            out_bf16=lps if has_lp else None, table=table)
+                            out_bf16=lps if has_lp else None, table=table, emas=emas, ema_decay=ema_decay,
+                            ema_table=ema_table)
                 self._refresh_copies(ps, lp_other)
         return loss

@@ -530,6 +530,24 @@ class FullyShardedDataParallel(nn.Module):
         for u in self.all_units():
             u.refresh_lp()
 
+    @torch.no_grad()
+    def swap_ema_(self, optimizer):
+        """Put the parameter averages (``ema_decay``: optimizer state of the flat shards, so 1/world per rank) into
+        the model, or take them out again: the fused optimizer exchanges each flat master shard with its average and
+        writes ``lp_shard`` in the same launch; a unit still holding gathered parameters (SHARD_GRAD_OP units and
+        the root after a no-grad forward) drops them, as in ``load_state_dict``, so the next forward gathers the new
+        shards.  Every rank calls it, at a step boundary (no forward or backward in flight)."""
+        if not hasattr(optimizer, "swap_ema_"):
+            raise RuntimeError("FullyShardedDataParallel.swap_ema_() needs a fused optimizer (FusedAdamW, FusedSGD)")
+        optimizer.swap_ema_()
+        for u in self.all_units():
+            u.refresh_lp()              # a non-bf16 lp_shard the kernel did not write (fp32 compute on CPU)
+            if self.comm.world_size > 1:
+                if u.state == u.GATHERING:
+                    u.wait()
+                if u.state == u.GATHERED:
+                    u._free_full()
+
     def clip_grad_norm_(self, max_norm: float, norm_type: float = 2.0):
         """Global grad norm over all shards (one 1-float all-reduce) and in-place clipping."""
         from ..optim.clip import clip_grad_norm_

@@ -200,6 +200,23 @@ class OSS(Optimizer):
         self._exchange()
         return loss
 
+    @property
+    def ema_swapped(self) -> bool:
+        return bool(getattr(self.optim, "ema_swapped", False))
+
+    @torch.no_grad()
+    def swap_ema_(self):
+        """Put the parameter averages (``ema_decay``; each rank holds those of its own segment only) into the
+        parameters on every rank: the wrapped fused optimizer exchanges its owned parameters with their averages,
+        then the usual post-step all-gather hands every rank's replicas (and the ``broadcast_fp16`` payload) the
+        owners' averaged segments.  The same call swaps back.  A collective: every rank calls it, at a step
+        boundary."""
+        if self.optim is not None:
+            if not self._fused:
+                raise RuntimeError("OSS.swap_ema_() needs a fused optimizer (FusedAdamW, FusedSGD)")
+            self.optim.swap_ema_()
+        self._exchange()
+
     def _exchange(self):
         """Owners -> everyone: ONE all-gather per bank of the owners' (payload) segments."""
         with prof.range("oss.all_gather"):

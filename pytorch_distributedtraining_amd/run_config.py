@@ -42,6 +42,7 @@ class RunConfig:
     activation_checkpointing: bool = False
     dropout: float = 0.0                    # GPT-2: embedding + residual dropout (embd_pdrop = resid_pdrop)
     drop_path: float = 0.0                  # SwinIR: stochastic depth (drop_path_rate, ramped over the blocks)
+    ema_decay: float = 0.0                  # parameter EMA kept by the fused optimizer step (0.0: off)
     bucket_cap_mb: float = 64.0
     first_bucket_mb: float = 8.0
     sync_batchnorm: bool = False

@@ -113,7 +113,7 @@ def run(cfg: RunConfig, optimizer_cls=None) -> dict:
                  fairscale_oss=cfg.fairscale_oss and distributed is not None,
                  fairscale_sddp=cfg.fairscale_sddp and distributed is not None,
                  fairscale_fsdp=distributed == "fsdp", configs=configs, verbose=False,
-                 fp8=cfg.precision == "fp8" and gpu)
+                 fp8=cfg.precision == "fp8" and gpu, param_ema_decay=cfg.ema_decay or None)
     dev = tr.device
     gen = torch.Generator(device=dev)
     gen.manual_seed(cfg.seed + 1000 * tr.rank)
@@ -212,12 +212,14 @@ def main(argv=None):
     ap.add_argument("--dropout", type=float, default=None, help="GPT-2 embedding + residual dropout rate")
     ap.add_argument("--drop-path", type=float, default=None, dest="drop_path",
                     help="SwinIR stochastic depth rate (drop_path_rate; upstream SwinIR defaults to 0.1)")
+    ap.add_argument("--ema-decay", type=float, default=None, dest="ema_decay",
+                    help="decay of the parameter EMA kept by the fused optimizer step (0 = off)")
     ap.add_argument("--local-rank", "--local_rank", type=int, default=None, dest="local_rank")
     a = ap.parse_args(argv)
     if a.local_rank is not None:
         os.environ.setdefault("LOCAL_RANK", str(a.local_rank))
     cfg = apply_env_overrides(load_config(a.config, steps=a.steps, batch_size_per_device=a.batch_size_per_device,
-                                          dropout=a.dropout, drop_path=a.drop_path))
+                                          dropout=a.dropout, drop_path=a.drop_path, ema_decay=a.ema_decay))
     res = run(cfg)
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res, default=str), flush=True)

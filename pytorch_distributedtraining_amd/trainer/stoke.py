@@ -147,7 +147,8 @@ class Trainer:
                  grad_clip=None, gpu: bool = False, fp16=None, distributed=None, fairscale_oss: bool = False,
                  fairscale_sddp: bool = False, fairscale_fsdp: bool = False, configs=None, info_rank=0,
                  verbose: bool = True, ema_weight: float = 0.1, comm: Comm | None = None, fp8: bool = False,
-                 lazy_loss_sync: bool = False, ema_print_every: int = 1, portable_checkpoint: bool = False):
+                 lazy_loss_sync: bool = False, ema_print_every: int = 1, portable_checkpoint: bool = False,
+                 param_ema_decay: float | None = None):
         """``fp8=True`` (with bf16 precision on GPU): every framework ``Linear`` of the model runs its forward,
         data- and weight-gradient GEMMs in fp8 with delayed scaling (``ops.fp8.fp8_autocast``); norms,
         attention, the loss and the optimizer stay bf16 / fp32.
@@ -156,7 +157,12 @@ class Trainer:
         every N-th call only (Stoke prints on every call; the others then issue nothing at all).
         ``portable_checkpoint``: ``save`` writes the model in its standard layout where the model defines one
         (``to_portable_state_dict``: Llama's fused wqkv / w13 split back into Meta's wq, wk, wv / w1, w3); ``load``
-        accepts either layout (``from_portable_state_dict``)."""
+        accepts either layout (``from_portable_state_dict``).
+        ``param_ema_decay`` (not ``ema_weight``, which is the loss meter's): an exponential moving average of the
+        fp32 parameters with this decay, kept as optimizer state by the fused optimizer's step kernel (sharded,
+        captured and checkpointed with it; ``optim.FusedOptimizer``).  ``averaged_parameters()`` runs a block --
+        validation -- with the averaged weights in the model; ``ema_state_dict()`` is the model state with them.
+        Needs AdamW / Adam / SGD (torch's or the fused classes): they map to the fused classes on CPU too."""
         self.verbose = verbose
         self.logger = RankLogger(info_rank, verbose)
         self._loss_fn = loss
@@ -180,6 +186,10 @@ class Trainer:
         if fp8 and not (self.gpu and self.fp16 == "bf16"):
             raise ValueError("Trainer(fp8=True) needs gpu=True and fp16='bf16' (fp8 GEMMs under a bf16 compute dtype)")
         self.fp8 = bool(fp8)
+        if param_ema_decay is not None and not 0.0 < float(param_ema_decay) < 1.0:
+            raise ValueError(f"Trainer(param_ema_decay=...) must be in (0, 1), got {param_ema_decay}")
+        self.param_ema_decay = None if param_ema_decay is None else float(param_ema_decay)
+        self._averaged = False     # inside averaged_parameters()
         self.ddp_config = find_config(configs, DDPConfig) or DDPConfig()
         self.amp_config = find_config(configs, AMPConfig) or AMPConfig()
         self.oss_config = find_config(configs, FairscaleOSSConfig) or FairscaleOSSConfig()
@@ -225,6 +235,12 @@ class Trainer:
         opt_cls = self._fused_equivalent(opt_spec.optimizer)
         fused_cls = isinstance(opt_cls, type) and issubclass(opt_cls, FusedOptimizer)
         kw = dict(opt_spec.optimizer_kwargs)
+        if self.param_ema_decay is not None:
+            if not fused_cls and opt_spec.optimizer is not torch.optim.Adam:
+                raise ValueError("Trainer(param_ema_decay=...) keeps the average in the fused optimizer's step kernel: "
+                                 "the optimizer must be AdamW, Adam or SGD (torch.optim's or FusedAdamW / FusedSGD), "
+                                 f"got {getattr(opt_spec.optimizer, '__name__', opt_spec.optimizer)}")
+            kw["ema_decay"] = self.param_ema_decay
         self._sharded_grads = False
         self.compute_dtype = None
         if fairscale_fsdp:
@@ -296,12 +312,14 @@ class Trainer:
     # ------------------------------------------------------------------ construction helpers
     def _fused_equivalent(self, cls):
         """torch AdamW / Adam / SGD -> the framework's fused AdamW / SGD on GPU (identical math and state layout).
-        A subclass of a torch optimizer is the user's own and stays as given."""
-        if self.gpu and cls in (torch.optim.AdamW, FusedAdamW):
+        A subclass of a torch optimizer is the user's own and stays as given.  With ``param_ema_decay`` the mapping
+        holds on CPU too (the fused classes' torch-op paths): the average lives in their step."""
+        on = self.gpu or self.param_ema_decay is not None
+        if on and cls in (torch.optim.AdamW, FusedAdamW):
             return FusedAdamW
-        if self.gpu and cls in (torch.optim.SGD, FusedSGD):
+        if on and cls in (torch.optim.SGD, FusedSGD):
             return FusedSGD
-        if self.gpu and cls is torch.optim.Adam:
+        if on and cls is torch.optim.Adam:
             return lambda params, **kw: FusedAdamW(params, decoupled=False, **kw)
         return cls
 
@@ -385,6 +403,8 @@ class Trainer:
         return (self._grad_accum_counter + 1) % self.grad_accum == 0
 
     def backward(self, loss):
+        if self._averaged:
+            raise RuntimeError("Trainer.backward() inside averaged_parameters(): the averaged weights are not trained")
         boundary = self._is_boundary()
         scaled = self.scaler.scale(loss) if self.scaler is not None else loss
         use_no_sync = (not boundary) and self.ddp_config.no_sync and hasattr(self._engine, "no_sync")
@@ -394,6 +414,8 @@ class Trainer:
         self._grad_accum_counter = (self._grad_accum_counter + 1) % self.grad_accum
 
     def step(self):
+        if self._averaged:
+            raise RuntimeError("Trainer.step() inside averaged_parameters(): the averaged weights are not trained")
         if self._grad_accum_counter != 0:
             return False   # not an accumulation boundary
         maybe_inject_fault(self._optimizer_steps)     # env-driven fault injection (tests of restart/resume)
@@ -488,6 +510,41 @@ class Trainer:
         if hasattr(self._engine, "zero_grad") and self._engine is not self._module:
             self._engine.zero_grad()
         self._optimizer.zero_grad(set_to_none=True)
+
+    # ------------------------------------------------------------------ parameter EMA
+    def _swap_ema(self):
+        opt, eng = self._optimizer, self._engine
+        if hasattr(eng, "sharding_strategy"):         # FSDP: flat shards + gathered copies
+            eng.swap_ema_(opt)
+        else:     # OSS: the owners' swap + the exchange; DDP / plain: replicated parameters, every rank alike
+            opt.swap_ema_()
+
+    @contextlib.contextmanager
+    def averaged_parameters(self):
+        """Run the block with the averaged weights (``param_ema_decay``) in the model -- fp32 masters, compute
+        copies and, under the sharded engines, every rank's replicas -- and put the trained weights back afterwards,
+        bit for bit.  For validation (``eval()`` / ``no_grad``); ``backward()`` and ``step()`` raise inside.  Enter
+        it between a backward and the next forward, on every rank (under OSS / FSDP entering and leaving are collectives).  Buffers
+        (BatchNorm statistics) are the live ones.  Before the first step the average is the parameters."""
+        if self.param_ema_decay is None:
+            raise RuntimeError("Trainer.averaged_parameters() needs Trainer(param_ema_decay=...)")
+        if self._averaged:
+            raise RuntimeError("Trainer.averaged_parameters() does not nest")
+        self._swap_ema()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._averaged = False
+
+    def ema_state_dict(self):
+        """The model state dict with the averaged parameters: layout and rank-0 semantics of the checkpoint's model
+        state (``save``).  Every rank calls it."""
+        with self.averaged_parameters():
+            sd = self._model_state()
+            # the plain-module state dict aliases the parameters: detach the values from the swap back
+            return {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in sd.items()} if sd else sd
 
     # ------------------------------------------------------------------ loss sync / printing
     def detach_and_sync_loss(self, loss, device=None, lazy: bool | None = None):
