@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from ..ops import bias_gelu, cross_entropy, flash_attn_qkvpacked
 from ..ops import dropout as D
+from ..ops.cross_entropy import check_regularisers
 from ..ops.embedding import Embedding
 from ..ops.fp8 import fp8_enabled, fp8_gelu_mlp, fp8_gelu_mlp_ok, fp8_recompute_safe
 from ..ops.linear import Linear, gelu_mlp, gelu_mlp_ok, linear, linear_bias_gelu, linear_bias_gelu_ok, linear_residual
@@ -49,8 +50,14 @@ class GPT2Config:
     embd_pdrop: float = 0.0
     resid_pdrop: float = 0.0
     attn_pdrop: float = 0.0
+    # label smoothing and z-loss (z * logsumexp(logits)^2, PaLM uses 1e-4) of the training loss, computed inside the
+    # fused cross-entropy kernels.  Training mode only: in eval() the head returns plain cross-entropy, so
+    # validation loss and perplexity stay comparable between runs with different settings.
+    label_smoothing: float = 0.0
+    z_loss: float = 0.0
 
     def __post_init__(self):
+        check_regularisers(self.label_smoothing, self.z_loss)
         if self.attn_pdrop != 0:
             raise ValueError("attn_pdrop != 0 is not supported: dropout on the attention probabilities needs a mask "
                              "inside the flash-attention kernels, which keep no probability matrix to drop")
@@ -281,6 +288,10 @@ class GPT2LMHeadModel(nn.Module):
         if labels is None:
             return logits
         # training: the gradient is written over the (dead) logits in the forward's single read; eval keeps them
+        cfg = self.config
+        if self.training and (cfg.label_smoothing != 0 or cfg.z_loss != 0):   # eval returns plain cross-entropy
+            return cross_entropy(logits, labels, inplace_backward=True, grad_in_forward=True,
+                                 label_smoothing=cfg.label_smoothing, z_loss=cfg.z_loss)
         return cross_entropy(logits, labels, inplace_backward=True, grad_in_forward=self.training)
 
 

@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import cross_entropy, rope_tables, swiglu
+from ..ops.cross_entropy import check_regularisers
 from ..ops.attention import flash_attn_gqa_packed
 from ..ops.rope import apply_rope_qk_
 from ..ops.embedding import Embedding
@@ -48,6 +49,14 @@ class LlamaConfig:
     # keeps its GEMM outputs (qkv, gate/up) and residual stream and recomputes only the norms, the attention
     # forward and SwiGLU when backward needs their outputs (utils.recompute) -- no GEMM runs twice
     checkpoint_policy: str = "full"
+    # label smoothing and z-loss (z * logsumexp(logits)^2, PaLM uses 1e-4) of the training loss, computed inside the
+    # fused cross-entropy kernels.  Training mode only: in eval() the model returns plain cross-entropy, so
+    # validation loss and perplexity stay comparable between runs with different settings.
+    label_smoothing: float = 0.0
+    z_loss: float = 0.0
+
+    def __post_init__(self):
+        check_regularisers(self.label_smoothing, self.z_loss)
 
     @property
     def head_dim(self):
@@ -214,6 +223,10 @@ class Llama(nn.Module):
         if labels is None:
             return logits
         # training: the gradient is written over the (dead) logits in the forward's single read; eval keeps them
+        cfg = self.config
+        if self.training and (cfg.label_smoothing != 0 or cfg.z_loss != 0):   # eval returns plain cross-entropy
+            return cross_entropy(logits, labels, inplace_backward=True, grad_in_forward=True,
+                                 label_smoothing=cfg.label_smoothing, z_loss=cfg.z_loss)
         return cross_entropy(logits, labels, inplace_backward=True, grad_in_forward=self.training)
 
 

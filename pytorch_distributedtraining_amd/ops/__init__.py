@@ -6,7 +6,7 @@ matmul-shaped) and fails loudly if that library is missing; CPU tensors use the 
 from . import _lib
 from .activations import bias_gelu, swiglu
 from .attention import flash_attn, flash_attn_qkvpacked
-from .cross_entropy import cross_entropy
+from .cross_entropy import CrossEntropyLoss, cross_entropy
 from .drop_path import DropPath, drop_path, drop_path_add, sample_scales
 from .dropout import Dropout
 from .fp8 import dequantize_fp8, fp8_autocast, quantize_fp8, scale_from_amax
@@ -23,6 +23,7 @@ __all__ = [
     "bias_gelu", "swiglu", "flash_attn", "flash_attn_qkvpacked", "cross_entropy", "quantize_fp8",
     "dequantize_fp8", "fp8_autocast", "scale_from_amax", "TensorTable", "adamw_step", "cast_f32_to_bf16", "clip_coef",
     "l2norm_sq", "scale_", "sgd_step", "swap_", "LayerNorm", "RMSNorm", "Dropout", "DropPath", "drop_path",
+    "CrossEntropyLoss",
     "drop_path_add", "sample_scales", "layer_norm", "rms_norm", "apply_rope", "rope_tables",
     "native_available",
 ]

@@ -43,6 +43,8 @@ class RunConfig:
     dropout: float = 0.0                    # GPT-2: embedding + residual dropout (embd_pdrop = resid_pdrop)
     drop_path: float = 0.0                  # SwinIR: stochastic depth (drop_path_rate, ramped over the blocks)
     ema_decay: float = 0.0                  # parameter EMA kept by the fused optimizer step (0.0: off)
+    label_smoothing: float = 0.0            # LMs and classifiers: cross-entropy label smoothing (training loss only)
+    z_loss: float = 0.0                     # same models: z * logsumexp(logits)^2 added to the loss (PaLM: 1e-4)
     bucket_cap_mb: float = 64.0
     first_bucket_mb: float = 8.0
     sync_batchnorm: bool = False

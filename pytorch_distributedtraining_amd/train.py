@@ -31,17 +31,20 @@ def build_model(cfg: RunConfig):
     m = cfg.model
     if cfg.drop_path != 0 and not m.startswith("swinir"):
         raise ValueError(f"drop_path is implemented for the swinir models only, not {m}")
+    reg = dict(label_smoothing=cfg.label_smoothing, z_loss=cfg.z_loss)
+    if (cfg.label_smoothing != 0 or cfg.z_loss != 0) and (m.startswith("swinir") or m == "srnet"):
+        raise ValueError(f"label_smoothing / z_loss belong to a cross-entropy loss, which {m} does not train with")
     if m.startswith("gpt2"):
         from .models import build_gpt2
         return build_gpt2(m, n_positions=max(1024, cfg.seq_len),
                           activation_checkpointing=cfg.activation_checkpointing,
-                          embd_pdrop=cfg.dropout, resid_pdrop=cfg.dropout), "lm"
+                          embd_pdrop=cfg.dropout, resid_pdrop=cfg.dropout, **reg), "lm"
     if cfg.dropout != 0:
         raise ValueError(f"dropout is implemented for the gpt2 models only, not {m}")
     if m.startswith("llama"):
         from .models.llama import build_llama
         return build_llama(m, max_seq_len=max(cfg.seq_len, 2048),
-                           activation_checkpointing=cfg.activation_checkpointing), "lm"
+                           activation_checkpointing=cfg.activation_checkpointing, **reg), "lm"
     if m.startswith("resnet"):
         from .models import resnet
         return getattr(resnet, m)(num_classes=cfg.num_classes), "cls"
@@ -74,6 +77,9 @@ def loss_fn(cfg: RunConfig, kind: str):
     if kind == "lm":
         return lambda out, _tgt: out                      # the model returns the fused CE loss
     if kind == "cls" or cfg.loss == "ce":
+        if cfg.label_smoothing != 0 or cfg.z_loss != 0:
+            from .ops import cross_entropy
+            return lambda out, tgt: cross_entropy(out, tgt, label_smoothing=cfg.label_smoothing, z_loss=cfg.z_loss)
         return lambda out, tgt: F.cross_entropy(out.float(), tgt)
     if cfg.loss == "feat":
         from .models.losses import feat_loss
@@ -214,12 +220,17 @@ def main(argv=None):
                     help="SwinIR stochastic depth rate (drop_path_rate; upstream SwinIR defaults to 0.1)")
     ap.add_argument("--ema-decay", type=float, default=None, dest="ema_decay",
                     help="decay of the parameter EMA kept by the fused optimizer step (0 = off)")
+    ap.add_argument("--label-smoothing", type=float, default=None, dest="label_smoothing",
+                    help="cross-entropy label smoothing of the LM and classifier training loss")
+    ap.add_argument("--z-loss", type=float, default=None, dest="z_loss",
+                    help="weight of z * logsumexp(logits)^2 in the LM and classifier training loss")
     ap.add_argument("--local-rank", "--local_rank", type=int, default=None, dest="local_rank")
     a = ap.parse_args(argv)
     if a.local_rank is not None:
         os.environ.setdefault("LOCAL_RANK", str(a.local_rank))
     cfg = apply_env_overrides(load_config(a.config, steps=a.steps, batch_size_per_device=a.batch_size_per_device,
-                                          dropout=a.dropout, drop_path=a.drop_path, ema_decay=a.ema_decay))
+                                          dropout=a.dropout, drop_path=a.drop_path, ema_decay=a.ema_decay,
+                                          label_smoothing=a.label_smoothing, z_loss=a.z_loss))
     res = run(cfg)
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res, default=str), flush=True)
