@@ -1,5 +1,5 @@
-// Multi-tensor optimizer-side kernels for gfx950: fused AdamW, fused SGD, fused L2-norm / non-finite check,
-// clip-coefficient, and in-place scale.  One launch covers every tensor in a list.
+// Multi-tensor optimizer-side kernels for gfx950: fused AdamW, fused SGD, two-stage fused LAMB, fused L2-norm /
+// non-finite check, clip-coefficient, and in-place scale.  One launch covers every tensor in a list.
 //
 // Replaces the per-parameter foreach chain torch runs for the reference's AdamW + clip_grad_norm_
 // (reference: Stoke-DDP.py:226-235 AdamW(lr, betas=(0.9,0.99), eps, wd), Stoke-DDP.py:253
@@ -245,6 +245,212 @@ __global__ __launch_bounds__(MT_THREADS) void sgd_mt_kernel(
     sgd_chunk<G, false, EMA>(mt, c, chunk, h, gs, E, ema_w);
 }
 
+// ---- LAMB (You et al., "Large Batch Optimization for Deep Learning"; apex FusedLAMB / timm Lamb without the clip).
+// Per logical tensor:  u = m_hat / (sqrt(v) / sqrt(1 - b2^t) + eps) + wd * p,  r = ||p|| / ||u||,  p -= lr * r * u.
+// The ratio needs the norms of the WHOLE tensor before any element moves, so the step is two passes over the 6-word
+// table with a tiny per-row reduction between them (and, where a tensor is cut by a rank boundary, the caller's
+// all-reduce of ``sums``).  Stage 2 recomputes u from (p, m, v) instead of reading a stored copy: the same bytes,
+// no [numel] fp32 scratch.
+struct LambHyper {
+  float lr, beta1, beta2, eps, wd;
+  float omb1, omb2;  // 1 - beta1, 1 - beta2 rounded from double: 1.f - 0.999f is 6e-5 (relative) off 0.001
+  float bc1;       // 1 - beta1^t
+  float bc2_sqrt;  // sqrt(1 - beta2^t)
+  int adapt;       // 0: r = 1 (wd == 0 without always_adapt: bias-corrected Adam)
+};
+
+// the per-row int table that goes with the block table: [first block, number of blocks, logical-tensor index]
+constexpr int LAMB_ROW = 3;
+
+__device__ __forceinline__ void lamb_bias(LambHyper& h, const float* __restrict__ dstep) {
+  if (dstep != nullptr) {   // graph-capturable: the step count lives on the device, bias corrections here
+    // 1 - beta^t = -expm1(t log1p(-(1 - beta))): exact to rounding where beta^t is close to 1
+    const float t = *dstep;
+    h.bc1 = -expm1f(t * log1pf(-h.omb1));
+    h.bc2_sqrt = sqrtf(-expm1f(t * log1pf(-h.omb2)));
+  }
+}
+
+__device__ __forceinline__ void lamb_moments(float& m, float& v, float g, const LambHyper& h) {
+  m = h.beta1 * m + h.omb1 * g;
+  v = h.beta2 * v + h.omb2 * g * g;
+}
+
+// The update direction from the NEW moments and the OLD parameter: the ONE function both stages call.  The compiler
+// may still contract it differently at its two inline sites, so stage 2's u need not be the bit pattern stage 1
+// summed; that is accepted -- the sums only enter through the ratio of two norms.
+__device__ __forceinline__ float lamb_update(float p, float m, float v, const LambHyper& h) {
+  return (m / h.bc1) / (sqrtf(v) / h.bc2_sqrt + h.eps) + h.wd * p;
+}
+
+// Stage 1: new moments stored, u formed in registers, partial[2 * block] = (sum p*p, sum u*u) over the block's chunk.
+template <typename G>
+__global__ __launch_bounds__(MT_THREADS) void lamb_stage1_mt_kernel(
+    const int64_t* __restrict__ meta, const int* __restrict__ blk, int chunk, LambHyper h,
+    const float* __restrict__ gscale, const int* __restrict__ found_inf, const float* __restrict__ dstep,
+    float* __restrict__ partial) {
+  __shared__ float red[MT_THREADS / 64];
+  if (found_inf != nullptr && *found_inf != 0) return;  // GradScaler semantics: skip the step
+  const float gs = gscale ? *gscale : 1.f;
+  lamb_bias(h, dstep);
+  const int t = blk[2 * blockIdx.x], c = blk[2 * blockIdx.x + 1];
+  const int64_t* mt = meta + (int64_t)t * MT_META;
+  const float* __restrict__ P = reinterpret_cast<const float*>(mt[0]);
+  const G* __restrict__ Gr = reinterpret_cast<const G*>(mt[1]);
+  float* __restrict__ M = reinterpret_cast<float*>(mt[2]);
+  float* __restrict__ V = reinterpret_cast<float*>(mt[3]);
+  const int64_t n = mt[5];
+  const int64_t beg = (int64_t)c * chunk;
+  const int64_t end = beg + chunk < n ? beg + chunk : n;
+  const bool vec_ok = ((mt[0] | mt[1] | mt[2] | mt[3]) & 15) == 0 && (sizeof(G) == 4 || (mt[1] & 7) == 0);
+  float pp = 0.f, uu = 0.f;
+  int64_t i = beg + (int64_t)threadIdx.x * 4;
+  if (vec_ok) {
+    for (; i + 3 < end; i += MT_THREADS * 4) {
+      const f32x4 p = *reinterpret_cast<const f32x4*>(P + i);
+      f32x4 m = *reinterpret_cast<f32x4*>(M + i);
+      f32x4 v = *reinterpret_cast<f32x4*>(V + i);
+      float g[4];
+      if constexpr (sizeof(G) == 4) {
+        f32x4 gg = *reinterpret_cast<const f32x4*>(Gr + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = gg[k];
+      } else {
+        u16x4 gg = *reinterpret_cast<const u16x4*>(Gr + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = bf2f(gg[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float mk = m[k], vk = v[k];
+        lamb_moments(mk, vk, g[k] * gs, h);
+        const float u = lamb_update(p[k], mk, vk, h);
+        pp += p[k] * p[k];
+        uu += u * u;
+        m[k] = mk; v[k] = vk;
+      }
+      *reinterpret_cast<f32x4*>(M + i) = m;
+      *reinterpret_cast<f32x4*>(V + i) = v;
+    }
+    // tail (fewer than 4 left for this thread)
+    for (; i < end; ++i) {
+      const float p = P[i];
+      float m = M[i], v = V[i];
+      lamb_moments(m, v, to_f<G>(Gr[i]) * gs, h);
+      const float u = lamb_update(p, m, v, h);
+      pp += p * p;
+      uu += u * u;
+      M[i] = m; V[i] = v;
+    }
+  } else {
+    for (int64_t j = beg + threadIdx.x; j < end; j += MT_THREADS) {
+      const float p = P[j];
+      float m = M[j], v = V[j];
+      lamb_moments(m, v, to_f<G>(Gr[j]) * gs, h);
+      const float u = lamb_update(p, m, v, h);
+      pp += p * p;
+      uu += u * u;
+      M[j] = m; V[j] = v;
+    }
+  }
+  pp = block_sum<MT_THREADS / 64>(pp, red);
+  uu = block_sum<MT_THREADS / 64>(uu, red);
+  if (threadIdx.x == 0) {
+    partial[2 * (int64_t)blockIdx.x] = pp;
+    partial[2 * (int64_t)blockIdx.x + 1] = uu;
+  }
+}
+
+// One workgroup per row: the row's blocks are consecutive in the block table, so its partials are
+// partial[2 * first .. 2 * (first + count)).  Fixed order and no float atomics: bitwise reproducible.  sums is
+// zero-filled by the caller and a logical tensor sits on at most one row of a step, so a plain store is enough and a
+// rank holding no part of a tensor contributes 0 to the all-reduce.
+__global__ __launch_bounds__(MT_THREADS) void lamb_rowsum_kernel(const float* __restrict__ partial,
+                                                                 const int* __restrict__ rows,
+                                                                 const int* __restrict__ found_inf,
+                                                                 float* __restrict__ sums) {
+  __shared__ float red[MT_THREADS / 64];
+  if (found_inf != nullptr && *found_inf != 0) return;  // stage 1 wrote no partials
+  const int* r = rows + LAMB_ROW * (int64_t)blockIdx.x;
+  const int first = r[0], count = r[1], gid = r[2];
+  float pp = 0.f, uu = 0.f;
+  for (int b = threadIdx.x; b < count; b += MT_THREADS) {
+    pp += partial[2 * (int64_t)(first + b)];
+    uu += partial[2 * (int64_t)(first + b) + 1];
+  }
+  pp = block_sum<MT_THREADS / 64>(pp, red);
+  uu = block_sum<MT_THREADS / 64>(uu, red);
+  if (threadIdx.x == 0) {
+    sums[2 * (int64_t)gid] = pp;
+    sums[2 * (int64_t)gid + 1] = uu;
+  }
+}
+
+// Stage 2: r from the row's (all-reduced) sums, u recomputed through lamb_update, p / bf16 copy / EMA stored.
+template <bool EMA>
+__global__ __launch_bounds__(MT_THREADS) void lamb_stage2_mt_kernel(
+    const int64_t* __restrict__ meta, const int* __restrict__ blk, int chunk, LambHyper h,
+    const int* __restrict__ found_inf, const float* __restrict__ dstep, const int* __restrict__ rows,
+    const float* __restrict__ sums, const int64_t* __restrict__ ema_tab, float ema_w) {
+  if (found_inf != nullptr && *found_inf != 0) return;  // GradScaler semantics: skip the step
+  lamb_bias(h, dstep);
+  const int t = blk[2 * blockIdx.x], c = blk[2 * blockIdx.x + 1];
+  const int64_t* mt = meta + (int64_t)t * MT_META;
+  float* __restrict__ P = reinterpret_cast<float*>(mt[0]);
+  const float* __restrict__ M = reinterpret_cast<const float*>(mt[2]);
+  const float* __restrict__ V = reinterpret_cast<const float*>(mt[3]);
+  bf16_t* __restrict__ O = reinterpret_cast<bf16_t*>(mt[4]);
+  const int64_t ea = EMA ? ema_tab[t] : 0;
+  float* __restrict__ E = reinterpret_cast<float*>(ea);
+  const int gid = rows[LAMB_ROW * (int64_t)t + 2];
+  const float pn = sums[2 * (int64_t)gid], un = sums[2 * (int64_t)gid + 1];
+  const float ratio = (h.adapt && pn > 0.f && un > 0.f) ? sqrtf(pn) / sqrtf(un) : 1.f;
+  const float step = h.lr * ratio;
+  const int64_t n = mt[5];
+  const int64_t beg = (int64_t)c * chunk;
+  const int64_t end = beg + chunk < n ? beg + chunk : n;
+  const bool vec_ok = ((mt[0] | mt[2] | mt[3] | ea) & 15) == 0 && (mt[4] & 7) == 0;
+  int64_t i = beg + (int64_t)threadIdx.x * 4;
+  if (vec_ok) {
+    for (; i + 3 < end; i += MT_THREADS * 4) {
+      f32x4 p = *reinterpret_cast<f32x4*>(P + i);
+      const f32x4 m = *reinterpret_cast<const f32x4*>(M + i);
+      const f32x4 v = *reinterpret_cast<const f32x4*>(V + i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) p[k] -= step * lamb_update(p[k], m[k], v[k], h);
+      *reinterpret_cast<f32x4*>(P + i) = p;
+      if (EMA && E) {
+        f32x4 e = *reinterpret_cast<f32x4*>(E + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e[k] = ema_elem(e[k], p[k], ema_w);
+        *reinterpret_cast<f32x4*>(E + i) = e;
+      }
+      if (O) {
+        u16x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = f2bf(p[k]);
+        *reinterpret_cast<u16x4*>(O + i) = o;
+      }
+    }
+    // tail (fewer than 4 left for this thread)
+    for (; i < end; ++i) {
+      float p = P[i];
+      p -= step * lamb_update(p, M[i], V[i], h);
+      P[i] = p;
+      if (EMA && E) E[i] = ema_elem(E[i], p, ema_w);
+      if (O) O[i] = f2bf(p);
+    }
+  } else {
+    for (int64_t j = beg + threadIdx.x; j < end; j += MT_THREADS) {
+      float p = P[j];
+      p -= step * lamb_update(p, M[j], V[j], h);
+      P[j] = p;
+      if (EMA && E) E[j] = ema_elem(E[j], p, ema_w);
+      if (O) O[j] = f2bf(p);
+    }
+  }
+}
+
 // Sum of squares per block (ptr0 of each tensor), written to partial[blockIdx.x].
 template <typename G>
 __global__ __launch_bounds__(MT_THREADS) void l2norm_mt_kernel(const int64_t* __restrict__ meta,
@@ -479,6 +685,64 @@ PDT_API int pdt_sgd_ema_mt(const int64_t* meta, const int* blk, int nblocks, int
                                                                     ema_tab, ema_w);
   else
     return (int)hipErrorInvalidValue;
+  return (int)hipGetLastError();
+}
+
+// LAMB stage 1 over rows [param f32, grad, exp_avg f32, exp_avg_sq f32, bf16 out or null, numel]: stores the new
+// moments and partial[2 * block] = (sum p*p, sum u*u); partial holds 2 * nblocks floats.  omb = 1 - beta (rounded
+// from double by the caller), bc1 = 1 - beta1^t, bc2_sqrt = sqrt(1 - beta2^t); dstep (device, nullable) overrides both.
+PDT_API int pdt_lamb_stage1_mt(const int64_t* meta, const int* blk, int nblocks, int chunk, int grad_dtype, float beta1,
+                               float beta2, float omb1, float omb2, float eps, float wd, float bc1, float bc2_sqrt,
+                               const float* gscale, const int* found_inf, const float* dstep, float* partial,
+                               hipStream_t stream) {
+  LambHyper h{0.f, beta1, beta2, eps, wd, omb1, omb2, bc1, bc2_sqrt, 0};
+  if (nblocks <= 0) return 0;
+  if (partial == nullptr) return (int)hipErrorInvalidValue;
+  if (grad_dtype == kF32)
+    lamb_stage1_mt_kernel<float><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, dstep,
+                                                                     partial);
+  else if (grad_dtype == kBF16)
+    lamb_stage1_mt_kernel<bf16_t><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, gscale, found_inf, dstep,
+                                                                      partial);
+  else
+    return (int)hipErrorInvalidValue;
+  return (int)hipGetLastError();
+}
+
+// rows: 3 ints per table row [first block, block count, logical-tensor index]; sums[2 * index] = the row's
+// (sum p*p, sum u*u).  sums is zero-filled by the caller; an index sits on at most one row.
+PDT_API int pdt_lamb_rowsum(const float* partial, const int* rows, int nrows, const int* found_inf, float* sums,
+                            hipStream_t stream) {
+  if (nrows <= 0) return 0;
+  if (partial == nullptr || rows == nullptr || sums == nullptr) return (int)hipErrorInvalidValue;
+  lamb_rowsum_kernel<<<nrows, MT_THREADS, 0, stream>>>(partial, rows, found_inf, sums);
+  return (int)hipGetLastError();
+}
+
+// LAMB stage 2: p -= lr * r * u with r from sums (after the caller's all-reduce), adapt = 0 forces r = 1
+PDT_API int pdt_lamb_stage2_mt(const int64_t* meta, const int* blk, int nblocks, int chunk, float lr, float beta1,
+                               float beta2, float omb1, float omb2, float eps, float wd, float bc1, float bc2_sqrt,
+                               int adapt, const int* found_inf, const float* dstep, const int* rows,
+                               const float* sums, hipStream_t stream) {
+  LambHyper h{lr, beta1, beta2, eps, wd, omb1, omb2, bc1, bc2_sqrt, adapt};
+  if (nblocks <= 0) return 0;
+  if (rows == nullptr || sums == nullptr) return (int)hipErrorInvalidValue;
+  lamb_stage2_mt_kernel<false><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, found_inf, dstep, rows, sums,
+                                                                   nullptr, 0.f);
+  return (int)hipGetLastError();
+}
+
+// pdt_lamb_stage2_mt + parameter EMA (as pdt_adamw_ema_mt)
+PDT_API int pdt_lamb_stage2_ema_mt(const int64_t* meta, const int* blk, int nblocks, int chunk, float lr, float beta1,
+                                   float beta2, float omb1, float omb2, float eps, float wd, float bc1,
+                                   float bc2_sqrt, int adapt, const int* found_inf, const float* dstep,
+                                   const int* rows, const float* sums, const int64_t* ema_tab, float ema_w,
+                                   hipStream_t stream) {
+  LambHyper h{lr, beta1, beta2, eps, wd, omb1, omb2, bc1, bc2_sqrt, adapt};
+  if (nblocks <= 0) return 0;
+  if (rows == nullptr || sums == nullptr || ema_tab == nullptr) return (int)hipErrorInvalidValue;
+  lamb_stage2_mt_kernel<true><<<nblocks, MT_THREADS, 0, stream>>>(meta, blk, chunk, h, found_inf, dstep, rows, sums,
+                                                                  ema_tab, ema_w);
   return (int)hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-"""Multi-tensor launches: fused AdamW, fused SGD, fused L2 norm (+ non-finite check), clip coefficient, scale.
+"""Multi-tensor launches: fused AdamW, fused SGD, two-stage fused LAMB, fused L2 norm (+ non-finite check), clip coefficient, scale.
 
 One HIP launch covers an arbitrary list of tensors through a device-resident table
 (``csrc/kernels/multi_tensor.hip``).  The engines keep parameters/gradients in flat buffers so their
@@ -115,11 +115,50 @@ class PointerTable:
         return self._key
 
 
+class RowTable:
+    """Three int32 words per row of a ``TensorTable`` -- [first block, block count, logical-tensor index] -- for the
+    LAMB kernels: a row's blocks are consecutive in the block table, so its per-block partial sums are one span, and
+    ``gids[row]`` names the logical tensor whose norms the row adds to (a row is a whole tensor or the local part of
+    one).  A logical tensor sits on at most one row."""
+
+    def __init__(self, table: TensorTable, gids: Sequence[int]):
+        gids = [int(g) for g in gids]
+        assert len(gids) == len(table.numels)
+        assert len(set(gids)) == len(gids), "a logical tensor may sit on one table row only"
+        n = len(gids)
+        dev = table.device
+        host = torch.zeros(max(n, 1), 3, dtype=torch.int32, pin_memory=dev.type == "cuda")
+        if n:
+            counts = torch.tensor([(m + table.chunk - 1) // table.chunk for m in table.numels], dtype=torch.int64)
+            host[:, 0] = (torch.cumsum(counts, 0) - counts).to(torch.int32)
+            host[:, 1] = counts.to(torch.int32)
+            host[:, 2] = torch.tensor(gids, dtype=torch.int32)
+        if dev.type == "cuda":
+            self.rows = host.to(dev, non_blocking=True)
+            self._host = host                                 # pinned source stays alive with the table
+        else:
+            self.rows = host
+        self.nrows = n
+        self.gids = gids
+        self.max_gid = max(gids) if gids else -1
+        self._key = (table.key(), tuple(gids))
+
+    def key(self) -> tuple:
+        return self._key
+
+
 class TableCache:
     """Rebuilds a TensorTable only when the pointer set changes."""
 
     def __init__(self):
         self._tables = {}
+
+    def get_rows(self, name, table: TensorTable, gids) -> RowTable:
+        t = self._tables.get(name)
+        if t is None or t.key() != (table.key(), tuple(gids)):
+            t = RowTable(table, gids)
+            self._tables[name] = t
+        return t
 
     def get_pointers(self, name, tensors, like) -> PointerTable:
         key = TensorTable.make_key([tensors])
@@ -384,6 +423,157 @@ def sgd_step(params, grads, bufs, *, lr, momentum: float, weight_decay: float, n
     _lib.call("pdt_sgd_mt", table.meta.data_ptr(), table.blk.data_ptr(), table.nblocks, table.chunk,
               _lib.dtype_code(gdt), lr_val, float(momentum), float(weight_decay), 1 if nesterov else 0,
               _lib.ptr(grad_scale), _lib.ptr(found_inf), lr_ptr, _lib.stream_handle(dev))
+
+
+def _lamb_bias(beta1, beta2, step, dstep, params):
+    if dstep is not None and params and params[0].device.type != "cuda":
+        step = int(dstep.item())
+    step = max(int(step), 1)
+    return 1.0 - beta1 ** step, math.sqrt(1.0 - beta2 ** step)
+
+
+def _lamb_u_cpu(p, m, v, bc1, bc2_sqrt, eps, wd):
+    """The LAMB update direction from the new moments and the old parameter (the kernels' ``lamb_update``)."""
+    return (m / bc1) / (v.sqrt() / bc2_sqrt + eps) + wd * p
+
+
+def _lamb_tables(name, params, grads, exp_avgs, exp_avg_sqs, out_bf16, gids, table, row_table):
+    if table is None:
+        cols = [list(params), list(grads), list(exp_avgs), list(exp_avg_sqs),
+                list(out_bf16) if out_bf16 is not None else [None] * len(params)]
+        table = _cache.get((name, grads[0].dtype, len(params), id(params[0])), cols)
+    if row_table is None:
+        row_table = _cache.get_rows((name + "-rows", grads[0].dtype, len(params), id(params[0])), table, gids)
+    if row_table.nrows != len(params) or list(row_table.gids) != [int(g) for g in gids]:
+        raise ValueError("lamb: the row table does not belong to these rows")
+    return table, row_table
+
+
+def lamb_stage1(params, grads, exp_avgs, exp_avg_sqs, sums: torch.Tensor, *, beta1: float, beta2: float, eps: float,
+                weight_decay: float, step: int, gids, grad_scale: torch.Tensor | None = None,
+                found_inf: torch.Tensor | None = None, out_bf16=None, table: TensorTable | None = None,
+                row_table: RowTable | None = None, dstep: torch.Tensor | None = None) -> None:
+    """First pass of ``lamb_step`` over one list of rows: the new moments are stored and ``sums[gids[i]]`` receives
+    row i's (``sum p*p``, ``sum u*u``) -- one stage-1 launch and one row-sum launch.  ``sums``: the caller's zeroed
+    ``[n_logical, 2]`` fp32 tensor (several row lists of one param group share it)."""
+    if len(params) == 0:
+        return
+    if sums.dtype != torch.float32 or sums.dim() != 2 or sums.shape[1] != 2 or not sums.is_contiguous() or \
+            sums.device != params[0].device:
+        raise TypeError("lamb: sums is a contiguous [n_logical, 2] fp32 tensor on the parameters' device")
+    if len(gids) != len(params) or min(gids) < 0 or max(gids) >= sums.shape[0]:
+        raise ValueError(f"lamb: one logical-tensor index in [0, {sums.shape[0]}) per row")
+    bc1, bc2_sqrt = _lamb_bias(beta1, beta2, step, dstep, params)
+    dev = params[0].device
+    if dev.type != "cuda":
+        if found_inf is not None and int(found_inf.reshape(-1)[0]) != 0:
+            return
+        gs = None if grad_scale is None else grad_scale.reshape(())
+        for i, p in enumerate(params):
+            g = grads[i].float()
+            if gs is not None:
+                g = g * gs
+            m, v = exp_avgs[i], exp_avg_sqs[i]
+            m.mul_(beta1).add_(g, alpha=1 - beta1)
+            v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+            u = _lamb_u_cpu(p, m, v, bc1, bc2_sqrt, eps, weight_decay)
+            sums[gids[i], 0] = (p * p).sum()
+            sums[gids[i], 1] = (u * u).sum()
+        return
+    gdt = grads[0].dtype
+    if gdt not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"lamb: gradients must be fp32 or bf16, got {gdt}")
+    table, row_table = _lamb_tables("lamb", params, grads, exp_avgs, exp_avg_sqs, out_bf16, gids, table, row_table)
+    partial = torch.empty(2 * max(table.nblocks, 1), dtype=torch.float32, device=dev)
+    st = _lib.stream_handle(dev)
+    _lib.call("pdt_lamb_stage1_mt", table.meta.data_ptr(), table.blk.data_ptr(), table.nblocks, table.chunk,
+              _lib.dtype_code(gdt), float(beta1), float(beta2), 1.0 - float(beta1), 1.0 - float(beta2), float(eps),
+              float(weight_decay), float(bc1), float(bc2_sqrt), _lib.ptr(grad_scale), _lib.ptr(found_inf), _lib.ptr(dstep), partial.data_ptr(), st)
+    _lib.call("pdt_lamb_rowsum", partial.data_ptr(), row_table.rows.data_ptr(), row_table.nrows, _lib.ptr(found_inf),
+              sums.data_ptr(), st)
+
+
+def lamb_stage2(params, exp_avgs, exp_avg_sqs, sums: torch.Tensor, *, lr: float, beta1: float, beta2: float,
+                eps: float, weight_decay: float, step: int, adapt: bool, gids, found_inf: torch.Tensor | None = None,
+                out_bf16=None, table: TensorTable | None = None, row_table: RowTable | None = None,
+                dstep: torch.Tensor | None = None, emas=None, ema_decay: float | None = None,
+                ema_table: PointerTable | None = None) -> None:
+    """Second pass of ``lamb_step``: ``p -= lr * r * u`` with ``r`` from ``sums[gids[i]]`` (all-reduced by the caller
+    where a logical tensor spans ranks), the bf16 copy and the parameter EMA -- one launch.  ``table`` / ``row_table``
+    are stage 1's."""
+    ema_w = _ema_weight(emas, ema_decay, "lamb_step", len(params))
+    if len(params) == 0:
+        return
+    bc1, bc2_sqrt = _lamb_bias(beta1, beta2, step, dstep, params)
+    dev = params[0].device
+    if dev.type != "cuda":
+        if found_inf is not None and int(found_inf.reshape(-1)[0]) != 0:
+            return
+        for i, p in enumerate(params):
+            u = _lamb_u_cpu(p, exp_avgs[i], exp_avg_sqs[i], bc1, bc2_sqrt, eps, weight_decay)
+            pn, un = sums[gids[i], 0], sums[gids[i], 1]
+            if adapt and float(pn) > 0 and float(un) > 0:
+                p.sub_(u * (lr * (pn.sqrt() / un.sqrt())))
+            else:
+                p.sub_(u * lr)
+            if ema_w is not None and emas[i] is not None:
+                _ema_cpu_(emas[i], p, ema_w)
+            if out_bf16 is not None and out_bf16[i] is not None:
+                out_bf16[i].copy_(p)
+        return
+    if table is None or row_table is None:
+        raise ValueError("lamb_stage2: pass the table and the row table stage 1 used")
+    args = (table.meta.data_ptr(), table.blk.data_ptr(), table.nblocks, table.chunk, float(lr), float(beta1),
+            float(beta2), 1.0 - float(beta1), 1.0 - float(beta2), float(eps), float(weight_decay), float(bc1),
+            float(bc2_sqrt), 1 if adapt else 0,
+            _lib.ptr(found_inf), _lib.ptr(dstep), row_table.rows.data_ptr(), sums.data_ptr())
+    if ema_w is not None:
+        if ema_table is None:
+            ema_table = _cache.get_pointers(("lamb-ema", len(params), id(params[0])), list(emas), list(params))
+        _lib.call("pdt_lamb_stage2_ema_mt", *args, ema_table.ptrs.data_ptr(), ema_w, _lib.stream_handle(dev))
+        return
+    _lib.call("pdt_lamb_stage2_mt", *args, _lib.stream_handle(dev))
+
+
+def lamb_step(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta2: float, eps: float,
+              weight_decay: float, step: int, adapt: bool, gids, n_logical: int, sums: torch.Tensor | None = None,
+              reduce=None, grad_scale: torch.Tensor | None = None, found_inf: torch.Tensor | None = None,
+              out_bf16=None, table: TensorTable | None = None, row_table: RowTable | None = None,
+              dstep: torch.Tensor | None = None, emas=None, ema_decay: float | None = None,
+              ema_table: PointerTable | None = None) -> torch.Tensor:
+    """One fused (multi-tensor) LAMB update.  fp32 params/state; grads fp32 or bf16.  Row i is logical tensor
+    ``gids[i]`` of ``n_logical``, or the local part of it:
+
+        g = grad * grad_scale;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g
+        u = (m / (1 - b1^t)) / (sqrt(v) / sqrt(1 - b2^t) + eps) + wd p
+        r = ||p|| / ||u||  if adapt and both norms > 0, else 1;   p -= lr r u
+
+    with the norms over the whole logical tensor and the parameter before the update.  On CUDA: stage 1 (moments,
+    per-block partial sums), the row sum, ``reduce(sums)`` when given (the all-reduce of an engine that cuts tensors
+    across ranks), stage 2 -- no host sync.  Returns ``sums``, the ``[n_logical, 2]`` fp32 device tensor of
+    (``||p||^2``, ``||u||^2``) (zero-filled here; pass one to reuse its storage).  The other arguments are
+    ``adamw_step``'s; ``row_table`` is the cached ``RowTable`` of ``gids`` that goes with ``table``."""
+    if len(params) == 0:
+        return sums if sums is not None else torch.zeros(int(n_logical), 2, dtype=torch.float32)
+    if sums is None:
+        sums = torch.zeros(int(n_logical), 2, dtype=torch.float32, device=params[0].device)
+    else:
+        if sums.shape[0] != int(n_logical):
+            raise ValueError(f"lamb_step: sums has {sums.shape[0]} rows for {n_logical} logical tensors")
+        sums.zero_()
+    gids = [int(g) for g in gids]
+    if params[0].device.type == "cuda":
+        table, row_table = _lamb_tables("lamb", params, grads, exp_avgs, exp_avg_sqs, out_bf16, gids, table,
+                                        row_table)
+    lamb_stage1(params, grads, exp_avgs, exp_avg_sqs, sums, beta1=beta1, beta2=beta2, eps=eps,
+                weight_decay=weight_decay, step=step, gids=gids, grad_scale=grad_scale, found_inf=found_inf,
+                out_bf16=out_bf16, table=table, row_table=row_table, dstep=dstep)
+    if reduce is not None:
+        reduce(sums)
+    lamb_stage2(params, exp_avgs, exp_avg_sqs, sums, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+                weight_decay=weight_decay, step=step, adapt=adapt, gids=gids, found_inf=found_inf, out_bf16=out_bf16,
+                table=table, row_table=row_table, dstep=dstep, emas=emas, ema_decay=ema_decay, ema_table=ema_table)
+    return sums
 
 
 def swap_(a_list: Sequence[torch.Tensor], b_list: Sequence[torch.Tensor], out_bf16=None,

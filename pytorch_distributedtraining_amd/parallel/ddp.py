@@ -29,6 +29,7 @@ import torch.nn as nn
 from ..utils import profiling as prof
 from ..utils.native import require_runtime
 from ._readiness import NullReadiness, Readiness
+from ._segments import Segments
 from .comm import Comm, default_comm
 
 _DT_ID = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.float64: 3}
@@ -121,6 +122,14 @@ class _FlatGroup:
             m._pdt_grad = self.flat_grad
             m._pdt_zero_grad = self.flat_grad.zero_   # optimizer.zero_grad() clears the accumulated flat grad
             self.master = m
+            self.set_segments()
+
+    def set_segments(self):
+        """Tell per-tensor optimizers (FusedLAMB) where the parameters lie in the flat master (parallel/_segments.py):
+        one span per parameter at its offset, every one whole on this rank (the gradients are all-reduced).  Bucket
+        alignment padding belongs to no span."""
+        self.master._pdt_segments = Segments([(self.offset_of[li], p.numel(), li) for li, p in enumerate(self.params)],
+                                             len(self.params), None)
 
     def gather_grads(self):
         """Single-process gradient stealing (DistributedDataParallel._steal_grads) with a compute copy: the
@@ -357,6 +366,7 @@ class DistributedDataParallel(nn.Module):
                 om._pdt_zero_grad = g.flat_grad.zero_
                 om._pdt_lp_version = om._version
                 g.master = om
+                g.set_segments()
 
     # ------------------------------------------------------------------ hooks (parallel/_readiness.py)
     def _launch(self, bid):

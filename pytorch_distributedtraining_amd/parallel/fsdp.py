@@ -42,6 +42,7 @@ import torch.nn as nn
 from ..ops import grad_slots
 from ..utils import profiling as prof
 from ..utils.native import require_runtime
+from ._segments import Segments
 from .comm import Comm, default_comm
 
 
@@ -98,6 +99,14 @@ class _Unit:
                 shard[a - s0:b - s0].copy_(t.detach().reshape(-1)[a - off:b - off].to(torch.float32))
         self.flat_param = nn.Parameter(shard)
         self.flat_param._pdt_unit = self
+        # per-tensor optimizers (FusedLAMB, parallel/_segments.py): the local part of every parameter of the unit, in
+        # shard coordinates; a parameter cut by the rank boundary has a span on both ranks, hence the comm
+        spans = []
+        for gid, (off, n) in enumerate(zip(self.offsets, self.numels)):
+            a, b = max(off, s0), min(off + n, s0 + self.shard_numel)
+            if a < b:
+                spans.append((a - s0, b - a, gid))
+        self.flat_param._pdt_segments = Segments(spans, len(self.numels), self.comm if ws > 1 else None)
         self.lp_shard = torch.empty(self.shard_numel, dtype=self.mp.param_dtype, device=self.device)
         self.flat_param._pdt_lp_shard = self.lp_shard
         self.refresh_lp(force=True)

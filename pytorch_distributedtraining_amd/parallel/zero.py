@@ -29,6 +29,9 @@ MI355X-first design (not Fairscale's per-rank broadcasts and per-parameter reduc
     asynchronously from the grad hooks, and freed -- per-rank gradient memory is ~1/world of the model.
     ``reduce_mode="all_reduce"`` is the ZeRO-1 gradient path (DDP + OSS): full gradients, bucketed
     all-reduces over the same flat.
+  * Per-tensor optimizers (``FusedLAMB``): the partition assigns WHOLE parameters to ranks (``greedy_partition``) and
+    the local optimizer steps them one by one (the module parameters, or one fp32 master per owned parameter), so
+    every logical tensor is whole on its owner: OSS sets no ``_pdt_segments`` and the step needs no collective.
   * Optimizer-state consolidation gathers flat per-key state slices (tensors, no pickled state), plus tiny
     all-reduces of the per-parameter step counts.
 """

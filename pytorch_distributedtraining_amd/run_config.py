@@ -83,11 +83,11 @@ def load_config(path: str, **overrides) -> RunConfig:
     return RunConfig(**data)
 
 
-OPTIMIZERS = ("adamw", "sgd")
+OPTIMIZERS = ("adamw", "sgd", "lamb")
 
 
 def optimizer_name(optimizer: Dict[str, Any]) -> str:
-    """The optional ``name`` of an optimizer dict (``adamw`` by default, or ``sgd``); the other keys are the
+    """The optional ``name`` of an optimizer dict (``adamw`` by default, ``sgd`` or ``lamb``); the other keys are the
     optimizer's keyword arguments."""
     name = str(optimizer.get("name", "adamw")).lower()
     if name not in OPTIMIZERS:

@@ -109,7 +109,10 @@ def run(cfg: RunConfig, optimizer_cls=None) -> dict:
     distributed = cfg.distributed if (world > 1 or cfg.distributed == "fsdp") else None
     opt_kw = dict(cfg.optimizer)
     opt_kw.pop("name", None)
-    opt_cls = optimizer_cls or {"adamw": torch.optim.AdamW, "sgd": torch.optim.SGD}[optimizer_name(cfg.optimizer)]
+    # torch has no LAMB: the fused class on CPU as well (its torch-op path)
+    from .optim import FusedLAMB
+    opt_cls = optimizer_cls or {"adamw": torch.optim.AdamW, "sgd": torch.optim.SGD,
+                                "lamb": FusedLAMB}[optimizer_name(cfg.optimizer)]
     opt = StokeOptimizer(optimizer=opt_cls, optimizer_kwargs=opt_kw)
     precision = None if cfg.precision == "fp32" else "bf16" if cfg.precision == "fp8" else cfg.precision
     tr = Trainer(model, optimizer=opt, loss=loss_fn(cfg, kind), batch_size_per_device=cfg.batch_size_per_device,

@@ -238,7 +238,7 @@ class Trainer:
         if self.param_ema_decay is not None:
             if not fused_cls and opt_spec.optimizer is not torch.optim.Adam:
                 raise ValueError("Trainer(param_ema_decay=...) keeps the average in the fused optimizer's step kernel: "
-                                 "the optimizer must be AdamW, Adam or SGD (torch.optim's or FusedAdamW / FusedSGD), "
+                                 "the optimizer must be AdamW, Adam or SGD (torch.optim's or FusedAdamW / FusedSGD) or FusedLAMB, "
                                  f"got {getattr(opt_spec.optimizer, '__name__', opt_spec.optimizer)}")
             kw["ema_decay"] = self.param_ema_decay
         self._sharded_grads = False
